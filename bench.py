@@ -32,6 +32,17 @@ exactly the same stream and example count.
 
 Launch: python bench.py [--gpus 1 --steps 20 --warmup 5]; for N > 1 the driver uses
 python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: set-up, warmup, the timed steps, the
+result line (the fields of everything else are null). --full adds what is reported next to
+it: the holdout accuracies (trained model, CPU fp32 and fp64 reference learners on the same
+stream), the serving wave's predict latency, the engine's forecast latency and its
+end-to-end JSON / DIB training rates; --latency-samples, --ref, --engine-latency and
+--engine-e2e size (or switch off) the parts of a --full run.
+--dump-outputs DIR writes what the last timed step left with the caller, as float32 /
+float64 .npy files: w.npy (the model after the last round's apply; w16.npy too for a bf16
+model) and totals.npy (loss sum, fitted examples, mistakes, squared error, table
+overflows). The stream is seeded, so equal arguments give equal inputs from run to run.
 """
 from __future__ import annotations
 
@@ -320,6 +331,13 @@ def main(argv=None) -> int:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported next to the headline: holdout "
+                         "accuracy against the CPU reference learners, predict latency, the "
+                         "engine's forecast latency and end-to-end rates")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the model and the running totals the "
+                         "last step left as DIR/<name>.npy (rank 0)")
     ap.add_argument("--spokes", type=int, default=16,
                     help="sequential spokes per GPU (the reference's default parallelism)")
     ap.add_argument("--rows", type=int, default=8192, help="examples per spoke per round")
@@ -581,19 +599,33 @@ def main(argv=None) -> int:
     elapsed = float(el[0].item())
     rounds = a.warmup + a.steps
 
+    # ---- what the last timed step left with the caller: the model and the running totals
+    if a.dump_outputs and rank == 0:
+        import numpy as np
+
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        outs = {"w": learner.w.detach().float().cpu().numpy(),
+                "totals": learner.cum.detach().double().cpu().numpy()}
+        if learner.w16 is not None:
+            outs["w16"] = learner.w16.detach().float().cpu().numpy()
+        for name, arr in outs.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
+
     # ---- model quality: the trained model and the CPU reference-semantics learner
-    test = synth_raw(space, 20000, start=TEST_START, seed=25)
-    testh = test.hashed(space)
+    full = bool(a.full)
+    test = synth_raw(space, 20000, start=TEST_START, seed=25) if full else None
+    testh = test.hashed(space) if full else None
 
     def accuracy(w: torch.Tensor) -> float:
         s = L.linear_predict(w.detach().float().cpu(), testh)
         return float(((s >= 0).float() * 2 - 1 == testh.y).float().mean())
 
-    acc = accuracy(learner.w) if rank == 0 else None
+    acc = accuracy(learner.w) if rank == 0 and full else None
     fitted = learner.running_totals()["fitted"]
     ref_acc = ref64_acc = ref64_maxdw = None
     P_ref = S * world
-    do_ref = a.ref == "on" or (a.ref == "auto" and rounds * B * world <= a.ref_max_examples)
+    do_ref = full and (a.ref == "on" or
+                       (a.ref == "auto" and rounds * B * world <= a.ref_max_examples))
     if rank == 0 and do_ref:
         # same global stream, same rounds: round k of rank r trained pool batch k % pool
         wref, dref = torch.zeros(space.dim), torch.zeros(space.dim + 2)
@@ -621,7 +653,7 @@ def main(argv=None) -> int:
     # ---- p50 single-point predict latency: the persistent serving wave reading a pinned
     # mailbox (raw tokens, hashed by the wave), against the trained fp32 model
     lat_us = []
-    if rank == 0 and on_gpu and a.latency_samples > 0:
+    if full and rank == 0 and on_gpu and a.latency_samples > 0:
         from omldm_amd.ops.serving import PredictServer
 
         torch.cuda.synchronize(device)
@@ -641,10 +673,10 @@ def main(argv=None) -> int:
     p50 = statistics.median(lat_us) if lat_us else None
     p99 = sorted(lat_us)[int(0.99 * (len(lat_us) - 1))] if lat_us else None
 
-    eng = engine_forecast_latency(a.engine_latency) if (rank == 0 and on_gpu and
+    eng = engine_forecast_latency(a.engine_latency) if (full and rank == 0 and on_gpu and
                                                          a.engine_latency > 0) else None
     e2e = engine_e2e_rate(a.engine_e2e, a.e2e_batch) \
-        if (rank == 0 and on_gpu and a.engine_e2e > 0) else None
+        if (full and rank == 0 and on_gpu and a.engine_e2e > 0) else None
     e2e_dib = engine_e2e_rate(a.engine_e2e, a.e2e_batch, fmt="dib") if e2e is not None else None
 
     total_examples = a.steps * B * world
@@ -659,7 +691,7 @@ def main(argv=None) -> int:
             "value": round(value, 1), "unit": "examples/s", "n_gpus": world,
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 4),
             "host_enqueue_ms_per_step": round(t_enq / a.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak",
+            "higher_is_better": True, "scaling": "weak", "full": full,
             "vs_baseline": round(value / base["value"], 2) if base else None,
             "baseline": {"value": base["value"], "source": base["source"],
                          "what": "reference-class CPU baseline (BASELINE.md: the reference "

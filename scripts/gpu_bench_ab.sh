@@ -1,8 +1,9 @@
 #!/bin/bash
 # bench.py A/B: each argument is a tag of extra bench flags (commas for spaces).
 set -e
-mkdir -p gpurun_out/r5
+OUT=${OMLDM_OUT:-out}  # where this script leaves its records
+mkdir -p $OUT/r5
 for tag in "$@"; do
   name=$(echo "$tag" | tr '=,-' '___')
-  timeout -k 10 300 python bench.py --steps 5 --warmup 2 $(echo "$tag" | tr ',' ' ') > gpurun_out/r5/bab_${name}.json 2> gpurun_out/r5/bab_${name}.err
+  timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 $(echo "$tag" | tr ',' ' ') > $OUT/r5/bab_${name}.json 2> $OUT/r5/bab_${name}.err
 done

@@ -3,8 +3,9 @@
 # stream and HBM-resident ingest.
 set -u
 R=${GRAFT_REPO_ROOT:-$PWD}
-mkdir -p $R/gpurun_out
+OUT=${OMLDM_OUT:-$R/out}  # where this script leaves its records
+mkdir -p $OUT
 cd $R
-timeout -k 10 240 python bench.py --learner LogisticRegression --steps 200 --warmup 20 > gpurun_out/cfg2_pinned.json 2> gpurun_out/cfg2_pinned.err || { tail -20 gpurun_out/cfg2_pinned.err; exit 3; }
-timeout -k 10 240 python bench.py --learner LogisticRegression --ingest device --steps 200 --warmup 20 > gpurun_out/cfg2_device.json 2> gpurun_out/cfg2_device.err || { tail -20 gpurun_out/cfg2_device.err; exit 3; }
-cat gpurun_out/cfg2_pinned.json gpurun_out/cfg2_device.json
+timeout -k 10 240 python bench.py --full --learner LogisticRegression --steps 200 --warmup 20 > $OUT/cfg2_pinned.json 2> $OUT/cfg2_pinned.err || { tail -20 $OUT/cfg2_pinned.err; exit 3; }
+timeout -k 10 240 python bench.py --full --learner LogisticRegression --ingest device --steps 200 --warmup 20 > $OUT/cfg2_device.json 2> $OUT/cfg2_device.err || { tail -20 $OUT/cfg2_device.err; exit 3; }
+cat $OUT/cfg2_pinned.json $OUT/cfg2_device.json

@@ -18,7 +18,9 @@ def _port():
 
 
 def test_collective_sweep_two_ranks():
-    env = dict(os.environ, OMP_NUM_THREADS="1")
+    # the gloo rehearsal on the CPU, whatever devices the host has
+    env = dict(os.environ, OMP_NUM_THREADS="1", HIP_VISIBLE_DEVICES="",
+               CUDA_VISIBLE_DEVICES="", OMLDM_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()),
            os.path.join(ROOT, "bench", "collective_sweep.py"), "--sizes", "4096,65536",

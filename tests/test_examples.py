@@ -26,7 +26,9 @@ def test_single_node_recipe_two_ranks(tmp_path):
     port = s.getsockname()[1]
     s.close()
     env = dict(os.environ, TOPICS=str(tmp_path / "topics"), NGPU="2", N="20000", PORT=str(port),
-               OMP_NUM_THREADS="1")
+               OMP_NUM_THREADS="1",
+               # CPU ranks over gloo, whatever devices the host has
+               HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="", OMLDM_DIST_BACKEND="gloo")
     out = subprocess.run(["bash", os.path.join(ROOT, "examples", "single_node.sh")], cwd=ROOT,
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-3000:])

@@ -20,7 +20,10 @@ def test_device_locality_fake_sysfs(tmp_path):
 
 
 def test_bind_is_noop_without_gpu(monkeypatch):
+    import torch
+
     monkeypatch.setenv("OMLDM_NUMA_BIND", "1")
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)  # also on a GPU host
     before = os.sched_getaffinity(0)
     info = T.bind_to_device(0)
     assert info["numa_node"] is None
