@@ -23,8 +23,18 @@
 //
 // Safety: the wave exits on the stop word or after `lifetime_us` of wall time
 // (s_memrealtime, 100 MHz), whichever comes first; every spin is bounded by it.
+//
+// Two kernels share the mailbox, the request line and the host side of a request:
+// * serve_kernel: M hashed-linear rows of one weight matrix (omldm_serve_start);
+// * serve_plan_kernel: a plan (serve_plan.h), one entry per pipeline — StandardScaler /
+//   MinMaxScaler (a per-lane (x − shift) / div) and PolynomialFeatures(2) (a product of two
+//   lanes) in front of a hashed-linear or dense ridge row, the K rows of a MultiClassPA
+//   (argmax on the device) or the k centroids of a K-means (argmin on the device), all
+//   evaluated by the one wave from the request line it already holds
+//   (omldm_serve_plan_start; CPU mirror: csrc/host/serve_plan_cpu.cpp).
 #include "common.h"
 #include "hash_dev.h"
+#include "serve_plan.h"
 
 #include <chrono>
 #include <cstdlib>
@@ -185,6 +195,213 @@ __global__ __launch_bounds__(64) void serve_kernel(const WT* __restrict__ w0,
   if (lane == 0) sys_store(&mb->alive, 0u);
 }
 
+// ---- the plan-driven wave ---------------------------------------------------------------
+// The same mailbox protocol, but each model is a plan entry (serve_plan.h): preprocessor
+// stages on the dense lanes, then a hashed or dense dot product, K hashed dot products and an
+// argmax, or k centroid distances and an argmin. The parameters come from one of two fp32
+// arenas (the request's bank word); the plan itself is copied into LDS when the wave starts.
+// Every plan entry was validated by omldm_serve_plan_start; the kernel still checks each
+// gather index against its region's width, as serve_kernel checks idx against dim.
+__device__ __forceinline__ int plan_word(const int* e, int i) {
+  return __builtin_amdgcn_readfirstlane(e[i]);
+}
+
+__global__ __launch_bounds__(64) void serve_plan_kernel(const int* __restrict__ plan, int M,
+                                                        const float* __restrict__ a0,
+                                                        const float* __restrict__ a1, int dn, int dc,
+                                                        int dim, int cspan, Mailbox* mb,
+                                                        unsigned long long lifetime_ticks) {
+  __shared__ int s_plan[kPlanMaxModels * kPlanWords];
+  const int lane = threadIdx.x;
+  const int nf = dn + dc;
+  for (int i = lane; i < M * kPlanWords; i += 64) s_plan[i] = plan[i];
+  __syncthreads();
+  const unsigned long long t_end = rt_now() + lifetime_ticks;
+  unsigned int last = sys_load(&mb->req[0]);
+  if (lane == 0) {
+    sys_store(&mb->t_start, t_end - lifetime_ticks);
+    sys_store(&mb->t_end, t_end);
+    sys_store(&mb->alive, 1u);
+  }
+  int polls = 0;
+  while (true) {
+    const unsigned int d = sys_load(&mb->req[lane]);  // the whole line in one read
+    const unsigned int seq = __builtin_amdgcn_readfirstlane(d);
+    if (seq == last) {
+      if (++polls >= 64) {  // re-check the clock / stop word every 64 polls
+        polls = 0;
+        bool quit = false;
+        if (lane == 0) {
+          const bool st = sys_load(&mb->stop) != 0u;
+          const bool late = rt_now() > t_end;
+          quit = st || late;
+          if (quit) {
+            sys_store(&mb->exit_reason, st ? 1u : 2u);
+            sys_store(&mb->t_exit, rt_now());
+          }
+        }
+        if (__builtin_amdgcn_readfirstlane(quit ? 1 : 0)) break;
+      }
+      __builtin_amdgcn_s_sleep(1);
+      continue;
+    }
+    const bool pl = (lane >= 2 && lane < 2 + nf) || lane == kBankWord;
+    const uint32_t x = wave_xor(pl ? line_mix(d, (uint32_t)lane) : 0u) ^ line_mix(seq, 0u);
+    const uint32_t csum = (uint32_t)__shfl((int)d, 1, 64);
+    if (__builtin_amdgcn_readfirstlane(x == csum ? 1 : 0) == 0) continue;  // torn: re-poll
+    const float* __restrict__ A = __builtin_amdgcn_readlane((int)d, kBankWord) ? a1 : a0;
+    // the decoded point: lane j < dn holds numerical value j, lanes [dn, nf) their field's
+    // hashed slot and sign (decoded once, as serve_kernel does; the same for every model)
+    const unsigned int fj = (unsigned int)__shfl((int)d, (lane + 2) & 63, 64);
+    const float x0 = lane < dn ? __uint_as_float(fj) : 0.f;
+    int cidx = -1;
+    float cval = 0.f;
+    if (lane >= dn && lane < nf) {
+      const int c = (int)fj;
+      if (cspan < 0) {  // raw binary wire: the 32-bit category token, hashed here
+        const int code = hash_token_dev(fj, lane - dn, dn, (uint32_t)((dim - dn - 1) / dc));
+        if (code != -1) {
+          cidx = code & 0x7fffffff;
+          cval = code < 0 ? -1.f : 1.f;
+        }
+      } else if (cspan > 0) {
+        const unsigned u = (unsigned)c & 0xFFFFu;
+        if (u != 0xFFFFu) {
+          cidx = dn + (lane - dn) * cspan + (int)(u & 0x7fffu);
+          cval = (u & 0x8000u) ? -1.f : 1.f;
+        }
+      } else if (c != -1) {
+        cidx = c & 0x7fffffff;
+        cval = c < 0 ? -1.f : 1.f;
+      }
+    }
+    float mine = 0.f;  // lane o keeps the result of the model whose output index is o
+    bool has = false;
+    for (int m = 0; m < M; ++m) {
+      const int* e = s_plan + m * kPlanWords;
+      const int kind = plan_word(e, kPlKind), flags = plan_word(e, kPlFlags);
+      const int ns = min(plan_word(e, kPlStages), kPlanMaxStages);
+      const int off = plan_word(e, kPlOff), width = plan_word(e, kPlWidth);
+      const int K = plan_word(e, kPlK);
+      // stages, on the dense lanes only
+      float v = x0;
+      int D = dn;
+      for (int s = 0; s < ns; ++s) {
+        const int* st = e + kPlStage0 + 4 * s;
+        const int type = plan_word(st, 0), pa = plan_word(st, 1), pb = plan_word(st, 2);
+        if (type == kPlanAffine) {
+          if (lane < D) v = (v - A[pa + lane]) / A[pb + lane];
+        } else {  // kPlanPoly2: lanes [D, D + D(D+1)/2) take the pair products
+          const int np = D * (D + 1) / 2;
+          const int j = lane - D;
+          const bool fresh = j >= 0 && j < np;
+          const int pw = fresh ? e[kPlPairs + ((pa + j) & 63)] : 0;
+          const float va = __shfl(v, pw & 63, 64), vb = __shfl(v, (pw >> 8) & 63, 64);
+          if (fresh) v = va * vb;
+          D = min(D + np, kPlanLanes);
+        }
+      }
+      float r;
+      if (kind == kPlanKmeans) {
+        // lane j owns centroid c0 + j; x_f is broadcast, the distance accumulates in column
+        // order with one fma per column (the arithmetic of kmeans_assign_kernel)
+        const int dd_w = min(D, width);
+        float bd = INFINITY;
+        int bi = 0x7fffffff;
+        for (int c0 = 0; c0 < K; c0 += 64) {
+          const int c = c0 + lane;
+          const bool on = c < K;
+          const float* __restrict__ cr = A + off + (size_t)(on ? c : 0) * width;
+          float dd = 0.f;
+          for (int f0 = 0; f0 < dd_w; f0 += 8) {  // 8 loads in flight, then the fma chain
+            float cf[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) cf[u] = f0 + u < dd_w ? cr[f0 + u] : 0.f;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+              if (f0 + u < dd_w) {
+                const float t = readlane_f(v, f0 + u) - cf[u];
+                dd = fmaf(t, t, dd);
+              }
+            }
+          }
+          if (on && dd < bd) {
+            bd = dd;
+            bi = c;
+          }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {  // wave argmin, the lowest index wins a tie
+          const float od = __shfl_xor(bd, o, 64);
+          const int oi = __shfl_xor(bi, o, 64);
+          if (od < bd || (od == bd && oi < bi)) {
+            bd = od;
+            bi = oi;
+          }
+        }
+        r = bi == 0x7fffffff ? 0.f : (float)bi;
+      } else {
+        // lanes [0, D) dense, [D, D + dc) the categorical slots (they keep their slots
+        // however wide the dense block became), then the bias lane
+        const int nc = (flags & kPlanFlagDense) ? 0 : dc;
+        const int src = (lane - D + dn) & 63;
+        const int ci = __shfl(cidx, src, 64);
+        const float cf = __shfl(cval, src, 64);
+        int idx = -1;
+        float val = 0.f;
+        if (lane < D) {
+          idx = lane;
+          val = v;
+        } else if (lane < D + nc) {
+          idx = ci;
+          val = cf;
+        } else if (lane == D + nc && (flags & kPlanFlagBias)) {
+          idx = width - 1;
+          val = 1.f;
+        }
+        if ((unsigned)idx >= (unsigned)width) {
+          idx = -1;
+          val = 0.f;
+        }
+        if (kind == kPlanLinear) {
+          r = wave_sum(idx >= 0 ? val * A[off + idx] : 0.f);
+          if (flags & kPlanFlagSign) r = r >= 0.f ? 1.f : -1.f;
+        } else {  // kPlanMulticlass: K rows, gathers in groups of 16, argmax (lowest index)
+          float best = -INFINITY;
+          int bk = 0;
+          for (int k0 = 0; k0 < K; k0 += 16) {
+            float g[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+              g[k] = (idx >= 0 && k0 + k < K) ? A[off + (size_t)(k0 + k) * width + idx] : 0.f;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+              if (k0 + k < K) {  // wave-uniform
+                const float sk = wave_sum(val * g[k]);
+                if (sk > best) {
+                  best = sk;
+                  bk = k0 + k;
+                }
+              }
+            }
+          }
+          r = (float)bk;
+        }
+      }
+      if (lane == plan_word(e, kPlOut)) {
+        mine = r;
+        has = true;
+      }
+    }
+    if (has) sys_store(&mb->result[lane], mine);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    if (lane == 0) sys_store(&mb->seq_done, seq);
+    last = seq;
+    polls = 0;
+  }
+  if (lane == 0) sys_store(&mb->alive, 0u);
+}
+
 }  // namespace omldm
 
 using namespace omldm;
@@ -230,6 +447,32 @@ OMLDM_API int omldm_serve_start(const void* w, const void* w1, int w_bf16, long 
     else OMLDM_SERVE(float, false);
   }
 #undef OMLDM_SERVE
+  return (int)hipGetLastError();
+}
+
+// The plan-driven wave (serve_plan_kernel). plan: n_models entries (serve_plan.h) in pinned,
+// mapped host memory — checked here, read once by the wave into LDS; arena0 / arena1: the two
+// parameter banks of arena_floats floats each (arena1 nullptr: both banks read arena0).
+// Returns a negative code (serve_plan.h) without launching when the plan is not safe to run.
+OMLDM_API int omldm_serve_plan_start(const int* plan, int n_models, const float* arena0,
+                                     const float* arena1, long long arena_floats, int dn, int dc,
+                                     int cspan, int dim, void* mailbox, long long lifetime_us,
+                                     void* stream) {
+  const int bad = plan_check(plan, n_models, arena_floats, dn, dc, dim);
+  if (bad) return bad;
+  if (!arena0 || !mailbox) return kPlanErrShape;
+  if (arena1 == nullptr) arena1 = arena0;
+  Mailbox* hmb = (Mailbox*)mailbox;
+  void *dmb = nullptr, *dplan = nullptr;
+  if (hipHostGetDevicePointer(&dmb, mailbox, 0) != hipSuccess || !dmb) return -3;
+  if (hipHostGetDevicePointer(&dplan, (void*)plan, 0) != hipSuccess || !dplan) return -3;
+  __atomic_store_n(&hmb->stop, 0u, __ATOMIC_SEQ_CST);
+  __atomic_store_n(&hmb->exit_reason, 0u, __ATOMIC_SEQ_CST);
+  __atomic_store_n(&hmb->alive, 0u, __ATOMIC_SEQ_CST);
+  const unsigned long long ticks = (unsigned long long)lifetime_us * 100ull;  // 100 MHz
+  hipLaunchKernelGGL(serve_plan_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
+                     (const int*)dplan, n_models, arena0, arena1, dn, dc, dim, cspan,
+                     (Mailbox*)dmb, ticks);
   return (int)hipGetLastError();
 }
 

@@ -90,7 +90,9 @@ def build_hip(force: bool = False, jobs: int = 8) -> str:
 def build_host(force: bool = False) -> str:
     os.makedirs(NATIVE, exist_ok=True)
     srcs = host_sources()
-    deps = [os.path.getmtime(s) for s in srcs] + [_newest_header(os.path.join(CSRC, "host"))]
+    # (serve_plan_cpu.cpp shares csrc/kernels/serve_plan.h with the serving kernel)
+    deps = [os.path.getmtime(s) for s in srcs] + [_newest_header(os.path.join(CSRC, "host")),
+                                                  _newest_header(os.path.join(CSRC, "kernels"))]
     if force or _stale(HOST_LIB, deps):
         cxx = os.environ.get("CXX", "g++")
         tmp = HOST_LIB + ".tmp"

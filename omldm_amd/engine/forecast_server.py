@@ -20,6 +20,18 @@ it for EVERY pipeline before taking the next one:
   predict kernels on a one-row batch on the lane's HIP stream (one stream sync per
   record).
 
+``--forecastServer plans`` (opt-in; ``auto`` / ``true`` / ``false`` are unchanged) puts more
+on the wave: ``reconfigure`` builds ONE serving plan (ops/serving.py: ``build_plan``) over
+every pipeline the plan-driven wave can evaluate — hashed-linear learners of either bias
+behind StandardScaler / MinMaxScaler / PolynomialFeatures(2), ORR, MultiClassPA, K-means —
+and two fp32 parameter arenas; ``publish`` has each served learner and preprocessor write
+its current parameters into the arena no request reads (``serving_write``: device to
+device, no host sync), handed over exactly like a weight bank. The wave's values are final
+predictions (sign / argmax / argmin on the device). NN, Hoeffding trees and pipelines
+past the wave's limits (64 lanes, 4 stages, degree-2 maps) keep the one-row predicts. A job
+whose pipelines are all plan-served runs the native lane, which needs no change: it sees
+``M`` outputs, none of them to be thresholded.
+
 Consistency (the reference serialises a spoke's predict and fit in one operator,
 FlinkSpoke.scala:97-105, so a prediction sees a model between two fits):
 
@@ -83,8 +95,11 @@ class ForecastServer:
     SPIN_S = 2e-3
     WARM_S = 50e-3
 
-    def __init__(self, job, lifetime_us: int = 2_000_000):
+    def __init__(self, job, lifetime_us: int = 2_000_000, plans: bool = False):
         self.job = job
+        self.plans = bool(plans)      # --forecastServer plans: the plan-driven wave
+        self._plan = None             # ops.serving.ServingPlan of the served pipelines
+        self._fam_names: list = []    # latency family of each served pipeline
         self.space = job.space
         self.consumer = job.fcst_in
         self.topic = job.cfg.predictionsTopic
@@ -165,6 +180,7 @@ class ForecastServer:
             self._stop_native()
             self._stop_wave()
             self._spec = None
+            self._plan = None
             self._served = []
             self._direct = []
             self._order = []
@@ -180,12 +196,18 @@ class ForecastServer:
             self._stop_native()
             self._stop_wave()
             self._spec = None
+            self._plan = None
             self._served, self._direct, self._order = [], [], []
             pipes = [self.job.pipes[pid] for pid in sorted(self.job.pipes)]
             self._order = [p.id for p in pipes]
             store = [p for p in pipes if p.store is not None]
-            if os.environ.get("OMLDM_FS_NOWAVE") or self.job.device.type != "cuda":
-                store = []  # diagnostics / CPU jobs: the lane without the wave
+            nowave = bool(os.environ.get("OMLDM_FS_NOWAVE")) or self.job.device.type != "cuda"
+            if nowave or self.plans:
+                # diagnostics / CPU jobs: the lane without the wave; plans mode: the store
+                # pipelines are entries of the plan like any other
+                store = []
+            if self.plans and not nowave:
+                self._configure_plan(pipes)
             if store:
                 by_bias: dict = {}
                 for p in store:
@@ -206,12 +228,40 @@ class ForecastServer:
                         b.copy_(W)
                     torch.cuda.synchronize(self.job.device)
                     self._bank, self._pend = 0, None
+            if self._plan is None:
+                self._fam_names = ["linear-store"] * len(self._served)
             waved = {pid for pid, _, _ in self._served}
             self._direct = [(p.id, p) for p in pipes if p.id not in waved]
             if self._direct and self._stream is None and self.job.device.type == "cuda":
                 self._stream = torch.cuda.Stream(self.job.device)
             if self._native_eligible():
                 self._start_native()
+
+    def _configure_plan(self, pipes: list) -> None:
+        """Under the lock (plans mode): one serving plan over every pipeline the wave can
+        evaluate — store pipelines of either bias (the bias is a field of the plan entry),
+        scaled / polynomial ones, ORR, MultiClassPA, K-means — and two parameter arenas, both
+        filled with the current parameters. The wave's values are final predictions, so
+        ``_served`` carries (id, output index, False) and ``_spec`` the output range."""
+        from omldm_amd.ops.serving import build_plan
+
+        plan = build_plan(pipes, self.space)
+        if not plan.served:
+            return
+        self._plan = plan
+        self._spec = (0, plan.n_out, None)
+        self._row0 = 0
+        self._served = [(pid, out, False) for pid, out in plan.served]
+        self._fam_names = [self.job.pipes[pid].learner.NAME for pid, _ in plan.served]
+        with self._pub_lock:
+            n = max(1, plan.arena_floats)
+            if self._banks is None or tuple(self._banks[0].shape) != (n,):
+                self._banks = [torch.empty(n, dtype=torch.float32, device=self.job.device)
+                               for _ in range(2)]
+            for b in self._banks:
+                plan.write(b)
+            torch.cuda.synchronize(self.job.device)
+            self._bank, self._pend = 0, None
 
     # ------------------------------------------------------------ native lane
     def _native_eligible(self) -> bool:
@@ -331,7 +381,7 @@ class ForecastServer:
     def _ensure_wave(self):
         """Under the lock: a live wave over the configured store rows (started on the
         first record, restarted after its lifetime)."""
-        from omldm_amd.ops.serving import PredictServer
+        from omldm_amd.ops.serving import PlanServer, PredictServer
 
         srv = self._server
         if srv is not None and srv.lib.omldm_serve_alive(srv.mb):
@@ -339,8 +389,11 @@ class ForecastServer:
         self._stop_wave()
         lo, hi, bias = self._spec
         b0, b1 = self._banks
-        srv = PredictServer(b0[lo:hi], self.space.dn, self.space.dc, bias,
-                            cat_span=self.space.cat_span, w1=b1[lo:hi])
+        if self._plan is not None:
+            srv = PlanServer(self._plan.table, b0, self.space, arena1=b1)
+        else:
+            srv = PredictServer(b0[lo:hi], self.space.dn, self.space.dc, bias,
+                                cat_span=self.space.cat_span, w1=b1[lo:hi])
         srv.start(lifetime_us=self.lifetime_us)
         self._server = srv
         return srv
@@ -381,10 +434,17 @@ class ForecastServer:
         """Copy the served store rows into the bank requests do not read (current stream,
         after the round's apply) and hand it to the lane with the copy's event."""
         with self._pub_lock:
-            spec, banks = self._spec, self._banks
+            spec, banks, plan = self._spec, self._banks, self._plan
             if spec is None or banks is None:
                 return
             lo, hi, _ = spec
+
+            def fill(bank):  # plans mode: every served pipeline's serving_write
+                if plan is not None:
+                    plan.write(bank)
+                else:
+                    bank[lo:hi].copy_(self.job.store.W[lo:hi], non_blocking=True)
+
             if self._native is not None and self._bank_word is not None:
                 # the native lane reads the bank named by a pinned word the GPU sets after
                 # the copy (stream order): alternate banks, the word flips when it is done
@@ -397,14 +457,14 @@ class ForecastServer:
                 cur = ctypes.c_uint32.from_address(self._bank_word).value & 1
                 prev = self._nat_target
                 target = self._nat_target = prev if cur != prev else 1 - prev
-                banks[target][lo:hi].copy_(self.job.store.W[lo:hi], non_blocking=True)
+                fill(banks[target])
                 check_rc = _lib().omldm_bank_word_set(
                     self._bank_word, target, torch.cuda.current_stream().cuda_stream)
                 if check_rc != 0:
                     raise RuntimeError(f"hipStreamWriteValue32 failed ({check_rc})")
                 return
             target = self._pend[0] if self._pend is not None else 1 - self._bank
-            banks[target][lo:hi].copy_(self.job.store.W[lo:hi], non_blocking=True)
+            fill(banks[target])
             ev = torch.cuda.Event()
             ev.record()
             self._pend = (target, ev)
@@ -517,8 +577,8 @@ class ForecastServer:
         # own one-row predict (the others), as if it were the only pipeline
         base = (t_w - t_in) if t_w is not None else 0.0
         if t_w is not None:
-            for pid, _, _ in self._served:
-                self._fam("linear-store", base)
+            for name in self._fam_names:
+                self._fam(name, base)
         for name, dt in fam_t:
             self._fam(name, (base if t_w is None else 0.0) + dt)
         return True

@@ -107,10 +107,12 @@ class Job:
         # (engine/forecast_server.py) on GPU ranks; otherwise batched with the training rows
         fs = str(cfg.forecastServer).lower()
         self.fserver = None
-        if fs in ("true", "1") or (fs == "auto" and self.device.type == "cuda"):
+        # "plans": the lane as with "true", its wave driven by a serving plan (scaled,
+        # polynomial, ORR, MultiClassPA and K-means pipelines on the wave as well)
+        if fs in ("true", "1", "plans") or (fs == "auto" and self.device.type == "cuda"):
             from omldm_amd.engine.forecast_server import ForecastServer
 
-            self.fserver = ForecastServer(self)
+            self.fserver = ForecastServer(self, plans=fs == "plans")
         self.ingest = TickIngest([self.train_in] if self.fserver else
                                  [self.train_in, self.fcst_in], cfg.batchSize,
                                  pinned=self.device.type == "cuda",

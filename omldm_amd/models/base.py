@@ -89,6 +89,19 @@ class Learner:
         """(loss_sum, score_sum, n) on labelled points as device scalars."""
         raise NotImplementedError
 
+    # ------------------------------------------------ resident plan serving
+    def serving_entry(self, d: int) -> dict | None:
+        """How the plan-driven serving wave scores this learner on a dense block of ``d``
+        lanes (ops/serving.py: build_plan): ``{"kind": "linear" | "multiclass" | "kmeans",
+        "width", "rows", "bias", "sign", "dense"}``, or None when it cannot (the pipeline
+        then keeps one-row predicts)."""
+        return None
+
+    def serving_write(self, dst: torch.Tensor) -> None:
+        """The current parameters into ``dst``, this learner's fp32 region (rows · width)
+        of a serving arena — on the current stream, no host synchronisation."""
+        raise NotImplementedError
+
     # ---------------------------------------------------------------- API maps
     def hyper_parameters(self) -> dict:
         """The user-visible hyper-parameters (engine-internal ``_``-keys left out)."""

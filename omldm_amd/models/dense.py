@@ -93,6 +93,16 @@ class ORR(Learner):
         w = self.weights()
         return batch.num.float() @ w[: self.d] + w[self.d]
 
+    def serving_entry(self, d):
+        if d != self.d:
+            return None
+        # a dense-only row: d weights, the intercept in the bias lane's slot d
+        return {"kind": "linear", "width": self.d + 1, "rows": 1, "bias": True, "sign": False,
+                "dense": True}
+
+    def serving_write(self, dst):
+        dst.copy_(self.weights(), non_blocking=True)
+
     def evaluate(self, batch):
         ok = ~torch.isnan(batch.y)
         e = (batch.y - self.predict(batch))[ok]
@@ -211,6 +221,15 @@ class KMeans(Learner):
     def predict(self, batch):
         a = D.kmeans_assign(batch.num.float(), None, self.C, None, None, want_assign=True)
         return a.float()
+
+    def serving_entry(self, d):
+        if d != self.d:
+            return None
+        return {"kind": "kmeans", "width": self.d, "rows": self.k, "bias": False,
+                "sign": False, "dense": False}
+
+    def serving_write(self, dst):
+        dst.copy_(self.C.reshape(-1), non_blocking=True)
 
     def evaluate(self, batch):
         x = batch.num.float()
@@ -339,6 +358,20 @@ class MultiClassPA(Learner):
 
     def predict(self, batch):
         return self.scores(batch).argmax(1).float()
+
+    def serving_entry(self, d):
+        # Behind a widening stage the compact (field-aware) categorical values of this
+        # learner sit at the WIDENED dense width, in training (ops/dense.py: cbase =
+        # batch.dn) and in scores() alike; the wave places them at space.dn, the linear
+        # learners' rule — so such a pipeline keeps its one-row predicts. Wide slots are
+        # absolute and do not move.
+        if d != self.space.dn and self.space.cat_span > 0:
+            return None
+        return {"kind": "multiclass", "width": self.dim, "rows": self.K, "bias": self.bias,
+                "sign": False, "dense": False}
+
+    def serving_write(self, dst):
+        dst.copy_(self.W.reshape(-1), non_blocking=True)  # fp32 rows, not the shadow
 
     def evaluate(self, batch):
         ok = ~torch.isnan(batch.y)

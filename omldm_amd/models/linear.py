@@ -348,6 +348,13 @@ class LinearLearner(Learner):
             return torch.where(s >= 0, 1.0, -1.0)
         return s
 
+    def serving_entry(self, d: int) -> dict | None:
+        return {"kind": "linear", "width": self.dim, "rows": 1, "bias": bool(self.rule.bias),
+                "sign": self.TASK == "classification", "dense": False}
+
+    def serving_write(self, dst: torch.Tensor) -> None:
+        dst.copy_(self._wread(), non_blocking=True)  # (the store row when attached)
+
     def evaluate(self, batch: HashedBatch):
         s = self.decision(batch)
         y = batch.y

@@ -50,6 +50,18 @@ class Preprocessor:
     def load_state_dict(self, sd: dict) -> None:
         pass
 
+    # resident plan serving (ops/serving.py: build_plan)
+    def serving_stage(self, d: int) -> tuple[str, int] | None:
+        """This preprocessor as a stage of the plan-driven serving wave on ``d`` dense lanes:
+        (``"affine"`` | ``"poly2"``, arena floats it needs), or None when the wave has no
+        such stage (the pipeline then keeps one-row predicts)."""
+        return None
+
+    def serving_write(self, dst: torch.Tensor) -> None:
+        """The current parameters into ``dst``, this stage's fp32 arena region (an affine
+        stage: shift[d] then div[d], the transform being (x − shift) / div) — on the
+        current stream, no host synchronisation."""
+
     def to_obj(self) -> dict:
         return {"name": self.NAME, "hyperParameters": self.hyper, "parameters": {
             k: (v.tolist() if torch.is_tensor(v) else v) for k, v in self.state_dict().items()}}
@@ -86,6 +98,24 @@ class StandardScaler(Preprocessor):
             self.count = P.welford_update(x, self.count, self.mean, self.m2)
         return P.standardize(x, self.mean, self.m2, self.count)
 
+    def serving_stage(self, d):
+        return "affine", 2 * d
+
+    def serving_write(self, dst):
+        d = dst.numel() // 2
+        if self.mean is None:  # no data yet: the identity
+            dst[:d].zero_()
+            dst[d:].fill_(1.0)
+            return
+        # scale_kernel's arithmetic: shift = (float)mean, sd = var > 0 ? (float)sqrt(var) : 1
+        # with var = count > 0 ? m2 / count : 0 (fp64; the copies round to fp32)
+        dst[:d].copy_(self.mean)
+        if self.count > 0:
+            var = self.m2 / self.count
+            dst[d:].copy_(torch.where(var > 0, var.sqrt(), torch.ones_like(var)))
+        else:
+            dst[d:].fill_(1.0)
+
     def state_dict(self):
         return {"count": self.count, "mean": self.mean, "m2": self.m2}
 
@@ -110,6 +140,22 @@ class MinMaxScaler(Preprocessor):
         if train:
             P.minmax_update(x, self.lo, self.hi)
         return P.minmax_scale(x, self.lo, self.hi)
+
+    def serving_stage(self, d):
+        return "affine", 2 * d
+
+    def serving_write(self, dst):
+        d = dst.numel() // 2
+        if self.lo is None:  # no data yet: the batched transform gives 0 (range ≤ 0)
+            dst[:d].zero_()
+            dst[d:].fill_(float("inf"))
+            return
+        # scale_kernel's arithmetic: range > 0 ? (x − lo) / range : 0 — a division by +inf
+        # yields that 0 (the shift is dropped there: lo is ±inf before the first batch)
+        rg = self.hi - self.lo
+        ok = rg > 0
+        dst[:d].copy_(torch.where(ok, self.lo, torch.zeros_like(rg)))
+        dst[d:].copy_(torch.where(ok, rg, torch.full_like(rg, float("inf"))))
 
     def state_dict(self):
         return {"min": self.lo, "max": self.hi}
@@ -145,6 +191,10 @@ class PolynomialFeatures(Preprocessor):
 
     def fit_transform(self, x, train):
         return P.poly_expand(x, self._index(x.shape[1], x.device))
+
+    def serving_stage(self, d):
+        # (no parameters: the wave reads the static pair table of pair_index from its plan)
+        return ("poly2", 0) if self.degree == 2 else None
 
     def pair_index(self, d: int, device) -> torch.Tensor:
         """int32 [np, 2] (a, b) of the degree-2 products appended after the d inputs (the

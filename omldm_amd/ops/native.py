@@ -212,6 +212,7 @@ HOST_SIGS = [
                                          f32, i32, vp, vp]),
     ("omldm_cpu_linear_predict", None, [vp, i64, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp,
                                         vp]),
+    ("omldm_cpu_serve_plan", i32, [vp, i32, vp, i64, i32, i32, i32, i32, vp, vp, vp]),
     ("omldm_synth_raw", None, [u64, i64, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, i32]),
     ("omldm_cpu_hash_raw", None, [vp, i64, i32, i32, i64, vp, i32]),
     ("omldm_cpu_linear_seq_round", i32, [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, i32,

@@ -77,7 +77,8 @@ class JobConfig:
     prefetch: str = "auto"                # read tick k+1 while tick k trains (auto: on GPU)
     ingestCUs: int = 32                   # GPU: CUs (one XCD) for ingest copies; 0 off (profiles/round5/e2e_*.json)
     ingestCopy: str = "pull"              # GPU staging copy: pull (kernel) | sdma (hipMemcpyAsync)
-    forecastServer: str = "auto"          # per-record forecasts on the resident serving wave (auto: GPU)
+    forecastServer: str = "auto"          # per-record forecasts on the resident serving wave (auto: GPU);
+                                          # plans: the plan-driven wave (scalers, poly2, ORR, MultiClassPA, K-means)
     pipelineStreams: int = 8              # GPU: pipelines of a tick train on up to this many streams
     fusePipelines: str = "true"           # GPU: hashed-linear pipelines sharing a prep: one launch
     routeAhead: str = "false"             # GPU: holdout route + v3 prep beside the previous round
