@@ -21,10 +21,14 @@ models — runs the v3 table scan (csrc/kernels/linear_scan3.hip: chunk Grams on
 cores, one scan workgroup per spoke with its updates in an LDS slot table; the shrinking
 rules carry the spoke's model scale σ through the chain) on the raw wire and on the
 engine's field-aware hashed batches (bench/learners.py --preset p16: 228–277 M ex/s at
-16 spokes, profiles/round6/learners_p16.json). What v3 does not take falls back, logged:
+16 spokes, profiles/round6/learners_p16.json). Batches without categorical columns
+(``--catFeatures 0``; hashed, or raw and then hashed first) with at most 256 dense columns
+take the dense round instead (csrc/kernels/linear_dense.hip: one wave per spoke, the
+spoke's columns in registers; every rule, λ > 0, bf16 models; several pipelines on one
+batch in one launch). What neither takes falls back, logged:
 raw batches of an unsupported shape without a shrink to v1 (csrc/kernels/linear_seq.hip);
-non-field-aware hashed batches, more than 32 categorical fields or R > 8192 rows per
-spoke to the spoke-table round (csrc/kernels/linear_spoke.hip: per-spoke LDS delta tables
+non-field-aware hashed batches with categorical columns, more than 32 categorical fields
+or R > 8192 rows per spoke to the spoke-table round (csrc/kernels/linear_spoke.hip: per-spoke LDS delta tables
 spilling to HBM, spoke_table.h, ≈1.2 M ex/s).
 """
 from __future__ import annotations
@@ -130,7 +134,7 @@ class LinearLearner(Learner):
             return False
         if isinstance(batch, RawBatch):
             return not self.seq_capable(batch, ctx)
-        return self.group_key(batch, ctx) is None
+        return self._scan_group_key(batch, ctx) is None
 
     @staticmethod
     def _seq_geometry(B: int, ctx: RoundContext) -> tuple[int, int]:
@@ -192,8 +196,47 @@ class LinearLearner(Learner):
         if not ctx.fused_delta:
             self.apply_delta()
 
+    # ------------------------------------------------------------ dense round
+    def _dense_eligible(self, batch) -> bool:
+        """A batch without categorical columns (hashed or raw) on a GPU trains through the
+        dense round (ops.linear.linear_dense_round)."""
+        return (L.DENSE_ROUND and self.w.is_cuda and batch.dc == 0
+                and L.dense_fits(batch.dn, batch.dc, self.rule.bias)
+                and batch.dn <= self.dim - 1 and self.rule.rule in L.V3_RULES)
+
+    def _fit_dense(self, batch: HashedBatch, ctx: RoundContext) -> None:
+        B = batch.B
+        S = max(1, int(ctx.spokes))
+        R = max(1, -(-B // S)) if B else 1
+        parts = max(1, int(ctx.reduce_parts)) if ctx.on_reduce_part is not None else 1
+        if B:
+            self.rule.tbase = float(self.t0 + 1 + self.steps)
+            L.linear_dense_round(self._wread(), batch.contiguous(), R, S, self.dacc, self.rule,
+                                 ctx.inv_p, cum=self.cum, parts=parts,
+                                 on_part=ctx.on_reduce_part)
+            self.steps += R
+        else:
+            self.dacc[self.dim:].zero_()  # no workers this round on this rank
+            if ctx.on_reduce_part is not None:  # still join every collective of the round
+                for k in range(parts):
+                    ctx.on_reduce_part(k, *L.part_bounds(self.dim, k, parts, self.dacc.is_cuda))
+        self._seq_pending = False
+        if not ctx.fused_delta:
+            self.apply_delta()
+
     # ------------------------------------------------------ several pipelines
     def group_key(self, batch, ctx: RoundContext):
+        """Learners whose rounds on ``batch`` can share ONE launch: a key, or None when this
+        one cannot. Dense-eligible batches (no categorical column) group by dimension, rule
+        family, variant, bias, shrink mode and model dtype — C, ε, lr, λ and the Pegasos
+        clock may differ, there is no shared prep; the others by their v3 prep."""
+        if batch.B > 0 and self._dense_eligible(batch):
+            r = self.rule
+            return ("dense", self.dim, r.rule, r.variant, bool(r.bias), L._s3_shrink(r)[0],
+                    self.w16 is not None)
+        return self._scan_group_key(batch, ctx)
+
+    def _scan_group_key(self, batch, ctx: RoundContext):
         """Learners whose rounds on ``batch`` can share ONE v3 launch (same prep, same rule
         family and variant, no shrink, fp32): a key, or None when this one cannot."""
         if not (self.w.is_cuda and self.seq_capable() and batch.B > 0):
@@ -218,8 +261,9 @@ class LinearLearner(Learner):
     def prepare_ahead(self, batch: HashedBatch, ctx: RoundContext, stream) -> bool:
         """Make the v3 prep of this learner's round on ``batch`` now, on ``stream``, and
         attach it to the spoke-padded batch its ``fit`` will use (engine/job.py: the next
-        tick's route + prep run beside the current round). False: no v3 round here."""
-        if self.group_key(batch, ctx) is None:
+        tick's route + prep run beside the current round). False: no v3 round here (the
+        dense round has no prep)."""
+        if self._scan_group_key(batch, ctx) is None:
             return False
         b = batch.spoke_padded(max(1, int(ctx.spokes)))
         R, S = self._seq_geometry(b.B, ctx)
@@ -236,9 +280,12 @@ class LinearLearner(Learner):
     @staticmethod
     def fit_group(learners: list, batch, ctx: RoundContext) -> None:
         """One round of every learner in ``learners`` (equal ``group_key``) on ``batch`` in
-        one launch (ops.linear.linear_scan3_round_multi) — each learner ends exactly as its
-        own ``fit`` would leave it."""
+        one launch (ops.linear.linear_scan3_round_multi, or linear_dense_round_multi for a
+        batch without categorical columns) — each learner ends exactly as its own ``fit``
+        would leave it."""
         first = learners[0]
+        if first._dense_eligible(batch):
+            return LinearLearner._fit_group_dense(learners, batch, ctx)
         hashed = False
         if isinstance(batch, RawBatch):
             rb = batch
@@ -266,13 +313,33 @@ class LinearLearner(Learner):
         if not ctx.fused_delta:  # the models averaged in one launch
             LinearLearner.apply_delta_group(learners)
 
+    @staticmethod
+    def _fit_group_dense(learners: list, batch, ctx: RoundContext) -> None:
+        if isinstance(batch, RawBatch):
+            batch = batch.hashed(learners[0].space)
+        b = batch.spoke_padded(max(1, int(ctx.spokes))).contiguous()
+        S = max(1, int(ctx.spokes))
+        R = max(1, -(-b.B // S)) if b.B else 1
+        for lr in learners:
+            lr.rule.tbase = float(lr.t0 + 1 + lr.steps)
+        L.linear_dense_round_multi([lr._wread() for lr in learners], b, R, S,
+                                   [lr.dacc for lr in learners], [lr.rule for lr in learners],
+                                   ctx.inv_p, [lr.cum for lr in learners])
+        for lr in learners:
+            lr._seq_pending = False
+            lr.steps += R
+        if not ctx.fused_delta:
+            LinearLearner.apply_delta_group(learners)
+
     def fit(self, batch: HashedBatch, ctx: RoundContext) -> None:
         if isinstance(batch, RawBatch):
-            if self.seq_capable(batch, ctx):
+            if not self._dense_eligible(batch) and self.seq_capable(batch, ctx):
                 return self._fit_raw(batch, ctx)
             batch = batch.hashed(self.space)
         # a holdout-routed tick: spoke s trains exactly the rows spoke s routed
         batch = batch.spoke_padded(max(1, int(ctx.spokes)))
+        if self._dense_eligible(batch):
+            return self._fit_dense(batch, ctx)
         if self._slots_scan_eligible(batch, ctx):
             return self._fit_slots(batch, ctx)
         B = batch.B

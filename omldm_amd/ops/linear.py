@@ -1,6 +1,7 @@
 """Linear-family ops: virtual-spoke training round, batched predict, round apply.
 
-GPU tensors → hand-written HIP kernels (csrc/kernels/linear_spoke.hip).
+GPU tensors → hand-written HIP kernels (csrc/kernels/linear_spoke.hip; batches without
+categorical columns: csrc/kernels/linear_dense.hip).
 CPU tensors → the C++ reference implementation (csrc/host/linear_cpu.cpp) with the
 identical semantics (golden oracle + CPU engine path).
 """
@@ -140,7 +141,8 @@ def linear_round(w: torch.Tensor, batch: HashedBatch, R: int, S: int, dacc: torc
     assert dacc.dtype == torch.float32
     assert cum is None or cum.dtype == torch.float64  # running totals, added in fp64
     num, cat, y = batch.num, batch.cat, batch.y
-    assert cat.dtype == (torch.int16 if batch.cat_span else torch.int32)
+    # (no categorical column: a field-aware space has cat_span 0 and an int16 [B, 0] cat)
+    assert cat.shape[1] == 0 or cat.dtype == (torch.int16 if batch.cat_span else torch.int32)
     # labels: fp32, or int8 on the compact classification wire (GPU kernel reads either)
     assert y.dtype == torch.float32 or (y.dtype == torch.int8 and rule.rule != RULE_EPS)
     assert rule.rule != RULE_PEGASOS or (rule.lam > 0 and rule.tbase >= 2), "Pegasos: λ > 0, T ≥ 2"
@@ -295,6 +297,107 @@ def _s3_shrink(rule: "LinearRule") -> tuple[int, float, float]:
         r = 1.0 - (rule.lr * rule.lam if rule.rule == RULE_LOGISTIC else rule.lam)
         return 1, float(r), 0.0
     return 0, 1.0, 0.0
+
+
+# ------------------------------------------------------------------ dense round (dc = 0)
+# Batches without categorical columns: one wave per (spoke, pipeline) keeps the spoke's
+# ≤ 256 dense columns in registers (csrc/kernels/linear_dense.hip) — exact sequential
+# spokes, every rule of V3_RULES, λ > 0, bf16 models. OMLDM_DENSE_ROUND=0 restores the
+# routing without it (A/B): the spoke-table round for hashed batches, v1 for raw ones.
+DENSE_MAX = 256
+DENSE_MAX_PIPES = 16
+DENSE_ROUND = os.environ.get("OMLDM_DENSE_ROUND", "1") != "0"
+# rounds / multi-pipeline launches run through the dense kernel in this process (tests)
+DENSE_ROUNDS = 0
+DENSE_MULTI_LAUNCHES = 0
+
+
+def dense_fits(dn: int, dc: int, bias: bool) -> bool:
+    """The dense round's shape: no categorical column, 1 ≤ dn + bias ≤ DENSE_MAX columns."""
+    return int(dc) == 0 and 1 <= int(dn) + int(bool(bias)) <= DENSE_MAX
+
+
+def _dense_launch(ws: list, batch, R: int, S: int, daccs: list, rules: list, inv_p: float,
+                  cums: list, stats: list) -> None:
+    import ctypes
+
+    M = len(ws)
+    r0, w0 = rules[0], ws[0]
+    dim = int(daccs[0].shape[0]) - 2
+    num, y = batch.num, batch.y
+    assert 1 <= M <= DENSE_MAX_PIPES and len(daccs) == M and len(rules) == M
+    assert batch.dc == 0 and dense_fits(batch.dn, 0, r0.bias) and batch.dn <= dim - 1
+    assert w0.is_cuda and all(w.dtype == w0.dtype and w.shape[0] == dim and w.is_cuda
+                              for w in ws), "one launch: equal dim, every model fp32 or bf16"
+    assert w0.dtype in (torch.float32, torch.bfloat16)
+    assert all(d.dtype == torch.float32 and d.is_cuda and d.shape[0] == dim + 2 for d in daccs)
+    assert all(c is None or (c.dtype == torch.float64 and c.is_cuda) for c in cums)
+    assert all(s is None or (s.is_cuda and s.dtype == torch.float32 and s.is_contiguous()
+                             and s.shape == (S, STAT_W)) for s in stats)
+    assert all(r.rule == r0.rule and r.variant == r0.variant and bool(r.bias) == bool(r0.bias)
+               and _s3_shrink(r)[0] == _s3_shrink(r0)[0] for r in rules), \
+        "one launch: one rule family, variant, bias and shrink mode"
+    assert r0.rule in V3_RULES
+    assert num.dtype in (torch.float32, torch.bfloat16)
+    assert y.dtype == torch.float32 or (y.dtype == torch.int8 and r0.rule != RULE_EPS)
+    assert num.is_contiguous() and y.is_contiguous()
+    assert all(t.is_cuda or t.is_pinned() for t in ((num, y) if batch.dn else (y,)))
+    assert r0.rule != RULE_PEGASOS or all(r.lam > 0 and r.tbase >= 2 for r in rules), \
+        "Pegasos: λ > 0, T ≥ 2"
+    h = native.hip()
+    wsb = _workspace(w0.device, int(h.omldm_linear_dense_ws_words(M, S)), key="dense_ws")
+    P = lambda ts: (ctypes.c_void_p * M)(*[ptr(t) for t in ts])  # noqa: E731
+    F = lambda vs: (ctypes.c_float * M)(*[float(v) for v in vs])  # noqa: E731
+    dp = native.dptr
+    check(h.omldm_linear_dense_round(
+        M, P(ws), P(daccs), P(cums), P(stats), F([r.C for r in rules]),
+        F([r.eps for r in rules]), F([r.lr for r in rules]), F([r.lam for r in rules]),
+        F([r.tbase for r in rules]), int(w0.dtype == torch.bfloat16),
+        dp(num) if batch.dn else None, int(num.dtype == torch.bfloat16), batch.dn, dp(y),
+        int(y.dtype == torch.int8), batch.B, R, S, dim, ptr(wsb), r0.rule, r0.variant,
+        int(bool(r0.bias)), _s3_shrink(r0)[0], float(inv_p), native.stream_of(w0)),
+        "omldm_linear_dense_round")
+
+
+def linear_dense_round(w: torch.Tensor, batch: HashedBatch, R: int, S: int, dacc: torch.Tensor,
+                       rule: LinearRule, inv_p: float, cum: torch.Tensor | None = None,
+                       stats: torch.Tensor | None = None, parts: int = 1, on_part=None) -> None:
+    """One Synchronous round of S exact sequential spokes on a batch without categorical
+    columns (GPU; ``dense_fits``), accumulated like ``linear_round``: σ·Δ·inv_p into the
+    dn + bias touched slots of ``dacc[:dim]`` (zero on entry), Σσ·inv_p and Σinv_p over the
+    spokes with rows into ``dacc[dim]`` / ``dacc[dim+1]``, the round totals into ``cum``,
+    per-spoke ``stats`` [S, 6] (optional). ``w``: the fp32 model or its bf16 copy. The
+    accumulator is complete after the one launch; ``on_part`` is then called for every
+    part with the slices of ``part_bounds``, so the caller issues the same collectives as
+    for the spoke-table round."""
+    if S <= 0 or batch.B == 0:
+        return
+    global DENSE_ROUNDS
+    DENSE_ROUNDS += 1
+    _dense_launch([w], batch, R, S, [dacc], [rule], inv_p, [cum], [stats])
+    if on_part is not None:
+        parts = max(1, int(parts))
+        dim = int(dacc.shape[0]) - 2
+        for k in range(parts):
+            on_part(k, *part_bounds(dim, k, parts, cuda=True))
+
+
+def linear_dense_round_multi(ws: list, batch: HashedBatch, R: int, S: int, daccs: list,
+                             rules: list, inv_p: float, cums: list | None = None) -> None:
+    """``linear_dense_round`` of M pipelines on ONE batch, ≤ 16 per launch (grid.y = the
+    pipeline): the rules share the family, variant, bias and shrink mode, the models the
+    dtype; C, ε, lr, λ and tbase are per pipeline. Each accumulator ends bit-equal to its
+    own ``linear_dense_round``."""
+    if S <= 0 or batch.B == 0:
+        return
+    global DENSE_ROUNDS, DENSE_MULTI_LAUNCHES
+    cums = cums if cums is not None else [None] * len(ws)
+    for i in range(0, len(ws), DENSE_MAX_PIPES):
+        j = i + DENSE_MAX_PIPES
+        DENSE_ROUNDS += 1
+        DENSE_MULTI_LAUNCHES += 1
+        _dense_launch(ws[i:j], batch, R, S, daccs[i:j], rules[i:j], inv_p, cums[i:j],
+                      [None] * len(ws[i:j]))
 
 
 # GPU kernel of the exact sequential round: "scan3" (linear_scan3.hip, default: LDS slot

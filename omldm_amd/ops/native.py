@@ -54,6 +54,11 @@ HIP_SIGS = [
                                    vp, vp, vp]),
     ("omldm_linear_apply", i32, [vp, vp, vp, i32, vp]),
     ("omldm_linear_apply_multi", i32, [i32, vp, vp, vp, i32, vp]),
+    ("omldm_linear_dense_max", i32, []),
+    ("omldm_linear_dense_ws_words", i64, [i32, i32]),
+    ("omldm_linear_dense_round", i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32,
+                                       vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, f32,
+                                       vp]),
     ("omldm_linear_seq_round", i32, [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32,
                                      vp, vp, i32, i32, f32, f32, f32, f32, i32, vp]),
     ("omldm_linear_seq_apply", i32, [vp, vp, i32, vp, i32, vp]),
