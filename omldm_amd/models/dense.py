@@ -254,9 +254,11 @@ class KMeans(Learner):
 # ---------------------------------------------------------------------- MultiClassPA
 class MultiClassPA(Learner):
     """K-prototype Passive-Aggressive classifier on hashed features (labels 0..K-1);
-    virtual spokes per round: on a GPU with the field-aware wire and K ≤ 16 the v3 table scan
-    (csrc/kernels/linear_scan3.hip: s3mc_scan_kernel), else the spoke tables
-    (csrc/kernels/multiclass_spoke.hip)."""
+    virtual spokes per round. On a GPU: a batch without categorical columns takes the dense
+    round (csrc/kernels/multiclass_dense.hip: the K × (dn + bias) prototypes in LDS, exact
+    sequential spokes, K ≤ 256, fp32 prototypes; ops/dense.py ``multiclass_dense_fits``);
+    the field-aware wire with K ≤ 16 the v3 table scan (csrc/kernels/linear_scan3.hip:
+    s3mc_scan_kernel); everything else the spoke tables (csrc/kernels/multiclass_spoke.hip)."""
 
     NAME = "MultiClassPA"
     TASK = "classification"
@@ -336,9 +338,17 @@ class MultiClassPA(Learner):
             return
         S = max(1, ctx.spokes)
         R = max(1, -(-batch.B // S))
-        if self.K == 2 and self._fit_two_classes(batch, ctx, R, S):
+        dense = (self.W.is_cuda and D.MC_DENSE and batch.dc == 0 and self.Wt is not None
+                 and self.Wt.dtype == torch.float32 and batch.dn <= self.dim - 1
+                 and D.multiclass_dense_fits(batch.dn, batch.dc, self.bias, self.K))
+        if not dense and self.K == 2 and self._fit_two_classes(batch, ctx, R, S):
             return
-        if D.multiclass_scan3_fits(batch, R, self.K, self.bias, self.Wt):
+        if dense:
+            # no categorical column: exact sequential spokes on the K × (dn + bias) dense
+            # prototypes in LDS, any K ≤ 256 (K = 2 included)
+            D.multiclass_dense_round(self.W, batch, R, S, self.K, self.variant, self.C,
+                                     self.bias, self.dacc, self.st)
+        elif D.multiclass_scan3_fits(batch, R, self.K, self.bias, self.Wt):
             # exact sequential spokes on the v3 table scan (K ≤ 16, field-aware wire)
             D.multiclass_scan3_round(self.Wt, batch, R, S, self.K, self.variant, self.C,
                                      self.bias, self.dacc, self.st)

@@ -169,6 +169,68 @@ def multiclass_round(W: torch.Tensor, batch: HashedBatch, R: int, S: int, nclass
             ptr(dacc), ptr(stats))
 
 
+# ------------------------------------------------------- dense MultiClassPA round (dc = 0)
+# Batches without categorical columns: one workgroup per spoke keeps the K × (dn + bias)
+# round-start prototypes and its private delta in LDS (csrc/kernels/multiclass_dense.hip) —
+# exact sequential spokes at any K ≤ 256. OMLDM_MC_DENSE=0 restores the routing without it.
+MC_DENSE = os.environ.get("OMLDM_MC_DENSE", "1") != "0"
+MC_DENSE_MAX_D = 256      # kMcdMaxD
+MC_DENSE_MAX_K = 256      # kMcdMaxK
+MC_DENSE_MAX_KD = 16384   # kMcdMaxKD: w0 + d in 128 KiB of LDS
+# rounds run through the dense kernel in this process (tests)
+MC_DENSE_ROUNDS = 0
+
+
+def multiclass_dense_fits(dn: int, dc: int, bias: bool, nclass: int) -> bool:
+    """The dense MultiClassPA round's shape (omldm_multiclass_dense_fits draws the same
+    line): no categorical column, 1 ≤ D = dn + bias ≤ 256 columns, 2 ≤ K ≤ 256 classes,
+    K·D ≤ 16384."""
+    D_ = int(dn) + int(bool(bias))
+    K = int(nclass)
+    return (int(dc) == 0 and int(dn) >= 0 and 1 <= D_ <= MC_DENSE_MAX_D
+            and 2 <= K <= MC_DENSE_MAX_K and K * D_ <= MC_DENSE_MAX_KD)
+
+
+def multiclass_dense_round(W: torch.Tensor, batch: HashedBatch, R: int, S: int, nclass: int,
+                           variant: int, C: float, bias: bool, dacc: torch.Tensor,
+                           stats: torch.Tensor) -> None:
+    """S exact sequential MultiClassPA spokes of R rows on a batch without categorical
+    columns (GPU; ``multiclass_dense_fits``), with the contract of ``multiclass_round``:
+    dacc[K, dim] += Σ_s Δ_s (only its columns [0, dn) and dim − 1 are written), stats[0..3]
+    += (loss, rows, mistakes, spokes with rows). ``W``: the fp32 prototypes [K, dim]. bf16 or
+    fp32 numerical features and fp32 or int8 labels are read as they are. One round launch
+    and one fold launch, no atomics: the same inputs give the same bits."""
+    from omldm_amd.ops.linear import _workspace
+
+    if S <= 0 or batch.B == 0:
+        return
+    K, dim = W.shape
+    num, y = batch.num, batch.y
+    dn = int(batch.dn)
+    assert K == nclass and batch.dc == 0 and multiclass_dense_fits(dn, 0, bias, nclass)
+    assert dn <= dim - 1
+    assert W.is_cuda and W.dtype == torch.float32 and W.is_contiguous()
+    assert dacc.is_cuda and dacc.dtype == torch.float32 and dacc.is_contiguous()
+    assert dacc.shape == W.shape
+    assert stats.is_cuda and stats.dtype == torch.float32 and stats.numel() >= 6
+    assert num.dtype in (torch.float32, torch.bfloat16) and y.dtype in (torch.float32, torch.int8)
+    assert num.is_contiguous() and y.is_contiguous() and int(num.shape[1]) == dn
+    assert all(t.is_cuda or t.is_pinned() for t in ((num, y) if dn else (y,)))
+    assert variant in (0, 1, 2) and C > 0
+    global MC_DENSE_ROUNDS
+    MC_DENSE_ROUNDS += 1
+    h = native.hip()
+    D_ = dn + int(bool(bias))
+    ws = _workspace(W.device, int(h.omldm_multiclass_dense_ws_words(nclass, D_, S)),
+                    key="mc_dense_ws")
+    dp = native.dptr
+    check(h.omldm_multiclass_dense_round(
+        ptr(W), dp(num) if dn else None, int(num.dtype == torch.bfloat16), dn, dp(y),
+        int(y.dtype == torch.int8), batch.B, R, S, dim, nclass, int(variant), float(C),
+        int(bool(bias)), ptr(dacc), ptr(stats), ptr(ws), native.stream_of(W)),
+        "omldm_multiclass_dense_round")
+
+
 def kmeans_seq(x: torch.Tensor, y: torch.Tensor | None, cent: torch.Tensor, n: torch.Tensor,
                cum: torch.Tensor | None) -> None:
     """Exact sequential (MacQueen) k-means over the rows of x, in order (GPU:
