@@ -304,21 +304,13 @@ class MultiClassPA(Learner):
         PA: ℓ/‖x‖²). So the round runs the binary v3 scan (its step chain is ~4× shorter
         than the K-score scan's) and the prototypes are rebuilt from v and the invariant
         sum. Same rows, same order, same running totals (hinge loss, margin ≤ 0 mistakes)."""
-        from omldm_amd.api.batch import RawBatch
-
         if not (self.W.is_cuda and os.environ.get("OMLDM_MC_BINARY", "1") != "0"
                 and self.Wt is not None and self.Wt.dtype == torch.float32
-                and getattr(batch, "cat_span", 0) > 0 and batch.dc > 0 and batch.y.is_cuda
-                and L.SEQ_KERNEL == "scan3"
-                and batch.dn + batch.dc * batch.cat_span <= self.dim - 1
-                and L.scan3_fits(batch.dn, batch.dc, R, self.bias)):
+                and L.compact_scan_fits(batch, R, self.bias, self.dim)):
             return False
         yf = batch.y.float()
-        yb = torch.where(yf == 0, 1.0, torch.where(yf == 1, -1.0, float("nan"))).contiguous()
-        rb = RawBatch(batch.num.float().contiguous(), batch.cat.contiguous(), yb,
-                      span=batch.cat_span, cbase=batch.dn)
-        if not L.scan3_eligible_compact(rb, R, self.bias, self.dim):
-            return False
+        yb = torch.where(yf == 0, 1.0, torch.where(yf == 1, -1.0, float("nan")))
+        rb = L.compact_raw(batch, batch.dn, yb)
         rule = L.LinearRule(rule=L.RULE_HINGE, variant=self.variant, C=2.0 * self.C,
                             bias=self.bias)
         if getattr(self, "_dacc2", None) is None:

@@ -15,23 +15,13 @@ published Passive-Aggressive family (Crammer et al. 2006) — SURVEY.md Appendix
 * ``RegressorPA`` ε-insensitive loss, same τ family, update sign(y − w·x)·τ·x.
 * ``LogisticRegression`` (extension, BASELINE.json config 2): SGD on the log loss.
 
-A round is S virtual spokes, each an exact sequential learner on its R-row shard. On a GPU
-every rule — the PA family, RegressorPA, logistic SGD, SVM's L2 shrink, Pegasos, bf16
-models — runs the v3 table scan (csrc/kernels/linear_scan3.hip: chunk Grams on the matrix
-cores, one scan workgroup per spoke with its updates in an LDS slot table; the shrinking
-rules carry the spoke's model scale σ through the chain) on the raw wire and on the
-engine's field-aware hashed batches (bench/learners.py --preset p16: 228–277 M ex/s at
-16 spokes, profiles/round6/learners_p16.json). Batches without categorical columns
-(``--catFeatures 0``; hashed, or raw and then hashed first) with at most 256 dense columns
-take the dense round instead (csrc/kernels/linear_dense.hip: one wave per spoke, the
-spoke's columns in registers; every rule, λ > 0, bf16 models; several pipelines on one
-batch in one launch). What neither takes falls back, logged:
-raw batches of an unsupported shape without a shrink to v1 (csrc/kernels/linear_seq.hip);
-non-field-aware hashed batches with categorical columns, more than 32 categorical fields
-or R > 8192 rows per spoke to the spoke-table round (csrc/kernels/linear_spoke.hip: per-spoke LDS delta tables
-spilling to HBM, spoke_table.h, ≈1.2 M ex/s).
+A round is S virtual spokes, each an exact sequential learner on its R-row shard. Which of
+the four round kernels (dense, v3 table scan, v1 / CPU oracle, spoke table) a round takes is
+decided in one place, ``LinearLearner.route``; its docstring holds the table.
 """
 from __future__ import annotations
+
+from dataclasses import dataclass
 
 import torch
 
@@ -40,6 +30,16 @@ from omldm_amd.models.base import Learner, RoundContext, hp_float, hp_int
 from omldm_amd.ops import linear as L
 
 _VARIANTS = {"PA": L.PA, "PA-I": L.PA1, "PA1": L.PA1, "PA-II": L.PA2, "PA2": L.PA2}
+
+
+@dataclass(frozen=True)
+class Route:
+    """How one round runs (``LinearLearner.route``)."""
+
+    kind: str     # "dense" | "scan" | "seq" | "table"
+    R: int        # rows per spoke
+    S: int        # spokes the kernel is launched with
+    hashed: bool  # the kernel reads a hashed batch (a raw one is hashed first)
 
 
 class LinearLearner(Learner):
@@ -112,146 +112,158 @@ class LinearLearner(Learner):
     def _wread(self) -> torch.Tensor:
         return self.w16 if self.w16 is not None else self.w
 
-    def seq_capable(self, batch=None, ctx: RoundContext | None = None) -> bool:
-        """Raw-wire rounds run the exact sequential Gram-scan kernels (PA family, RegressorPA,
-        logistic SGD; v3 or v1). The shrinking rules (L2 λ > 0, Pegasos) and bf16 models have
-        only the v3 form: on a GPU, where the v3 scan takes ``batch`` (None: the caller checks
-        the shape). Everything else hashes the batch and takes the spoke-table round."""
-        if not L.shrinks(self.rule) and self.w16 is None:
-            return self.rule.rule in L.SEQ_RULES
-        if not (self.w.is_cuda and L.SEQ_KERNEL == "scan3"):
-            return False
-        if batch is None:
-            return True
-        R, _ = self._seq_geometry(batch.B, ctx) if ctx is not None else (batch.B, 1)
-        return bool(batch.B) and L.scan3_eligible(batch, R, self.rule.bias)
+    def seq_capable(self) -> bool:
+        """This learner has an exact sequential round (PA family, RegressorPA, logistic SGD:
+        v3, v1 or the CPU oracle). The shrinking rules (L2 λ > 0, Pegasos) and bf16 models
+        have only the v3 form, on a GPU; whether it takes a given batch is ``route``'s call."""
+        return self._plain() or (self.w.is_cuda and L.SEQ_KERNEL == "scan3")
 
-    def reduce_parts_apply(self, batch, ctx: RoundContext) -> bool:
-        """The spoke-table round reduces its tables in key-range parts; the v3 table scan
-        completes the accumulator only at its round end (no part is final earlier), so a
-        batch it takes runs one reduce and one collective."""
-        if not self.supports_reduce_parts:
-            return False
-        if isinstance(batch, RawBatch):
-            return not self.seq_capable(batch, ctx)
-        return self._scan_group_key(batch, ctx) is None
+    def _plain(self) -> bool:
+        return not L.shrinks(self.rule) and self.w16 is None
 
     @staticmethod
-    def _seq_geometry(B: int, ctx: RoundContext) -> tuple[int, int]:
+    def _geometry(B: int, ctx: RoundContext, active: bool = False) -> tuple[int, int]:
+        """(R, S) of a round of B rows: S = ctx.spokes shards of R = ⌈B/S⌉ rows. ``active``
+        (the scan and seq rounds) drops the trailing spokes without rows from S; the dense
+        and spoke-table rounds keep them."""
         S = max(1, int(ctx.spokes))
         R = max(1, -(-B // S)) if B else 1
-        S = max(1, -(-B // R)) if B else S
+        if active and B:
+            S = max(1, -(-B // R))
         return R, S
 
-    def _slots_scan_eligible(self, batch, ctx: RoundContext | None = None) -> bool:
-        """The engine's field-aware hashed batches train through the v3 table scan, which
-        reads their compact int16 slots as they are; other hashed batches take the
-        spoke-table round."""
-        if not (type(batch) is HashedBatch and batch.cat_span > 0 and self.w.is_cuda
-                and self.seq_capable() and batch.B > 0 and 0 < batch.dc
-                and L.SEQ_KERNEL == "scan3"
-                and self.space.dn + batch.dc * batch.cat_span <= self.dim - 1):
-            return False
-        R, _ = self._seq_geometry(batch.B, ctx) if ctx is not None else (batch.B, 1)
-        return bool(L.scan3_fits(batch.dn, batch.dc, R, self.rule.bias))
+    def route(self, batch, ctx: RoundContext) -> Route:
+        """The kernel this learner's round on ``batch`` takes — what ``fit``, ``fit_group``,
+        ``group_key``, ``prepare_ahead`` and ``reduce_parts_apply`` all follow. Host queries
+        only (shapes, dtypes, device flags, the cached ``spoke_padded``); first match wins.
+        gpu: the model is on a GPU; v3on: ``L.SEQ_KERNEL == "scan3"``; plain: no shrink
+        (λ = 0, not Pegasos) and an fp32 model.
 
-    def _fit_slots(self, batch: HashedBatch, ctx: RoundContext) -> None:
-        num, y = batch.num.float().contiguous(), batch.y.float().contiguous()
-        R, _ = self._seq_geometry(batch.B, ctx)
-        rb = RawBatch(num, batch.cat.contiguous(), y, span=batch.cat_span, cbase=self.space.dn)
-        # a v3 prep made ahead for this batch (engine/job.py route stream, or the first
-        # pipeline of the tick that trains on it; ops.linear checks that it matches)
-        rb.prep = getattr(batch, "prep", None)
-        assert L.scan3_eligible_compact(rb, R, self.rule.bias, self.dim), "v3 shape check"
-        self._fit_raw(rb, ctx, hashed=True)
-        batch.prep = rb.prep
+        ====== ==================================================================== =====
+        batch  condition                                                            kind
+        ====== ==================================================================== =====
+        either gpu, ``L.DENSE_ROUND``, dc = 0, 1 ≤ dn + bias ≤ 256, dn ≤ dim − 1    dense
+               (hashed first if raw; linear_dense.hip)
+        raw    gpu, v3on, B > 0, ``L.scan3_eligible`` (≤ 32 fields, R ≤ 8192)       scan
+               (linear_scan3.hip on raw tokens)
+        raw    plain (GPU: v1 on [S, dim] replicas, linear_seq.hip, logged once;    seq
+               CPU: the raw oracle, rawwire.cpp; B = 0 included)
+        hashed exactly ``HashedBatch``, gpu, v3on, ``L.compact_scan_fits`` with     scan
+               cbase = space.dn (field-aware, B > 0, dc > 0, a v3 shape;
+               linear_scan3.hip on the compact slots)
+        either anything else (hashed first if raw; linear_spoke.hip)                table
+        ====== ==================================================================== =====
 
-    def _fit_raw(self, batch: RawBatch, ctx: RoundContext, hashed: bool = False) -> None:
+        Hashed batches are spoke-padded first. Dense and table rounds run S = ctx.spokes
+        spokes of R = ⌈B/S⌉ rows, idle spokes included; scan and seq rounds only the
+        ⌈B/R⌉ spokes with rows (``_geometry``)."""
+        r, gpu = self.rule, self.w.is_cuda
+        raw = isinstance(batch, RawBatch)
+        if not raw:
+            batch = batch.spoke_padded(max(1, int(ctx.spokes)))
         B = batch.B
-        R, S = self._seq_geometry(B, ctx)
-        on_gpu = self.w.is_cuda
-        # v3 (the table scan) keeps no dense replicas: its round end sums the spokes'
-        # updates from the sorted occurrence lists; v1 / v2 average [S, dim] replicas
-        use_rep = on_gpu and not (B and L.scan3_eligible(batch, R, self.rule.bias))
-        if use_rep:
-            if self.replicas is None or self.replicas.shape[0] < S:
-                self.replicas = torch.empty((S, self.dim), dtype=torch.float32, device=self.device)
-                self._rep_valid = False
-            if not self._rep_valid:
-                L.linear_seq_broadcast(self.w, self.replicas)
-                self._rep_valid = True
-        parts = max(1, int(ctx.reduce_parts)) if ctx.on_reduce_part is not None else 1
-        if B:
-            self.rule.tbase = float(self.t0 + 1 + self.steps)  # Pegasos' step clock
-            L.linear_seq_round(self._wread(), batch, R, S, self.dacc, self.rule, ctx.inv_p,
-                               cum=self.cum, replicas=self.replicas if use_rep else None,
-                               parts=parts, on_part=ctx.on_reduce_part, hashed=hashed)
-            self.steps += R
-        else:
-            self.dacc[self.dim:].zero_()
-            if ctx.on_reduce_part is not None:  # still join every collective of the round
-                for k in range(parts):
-                    ctx.on_reduce_part(k, *L.part_bounds(self.dim, k, parts, self.dacc.is_cuda))
-        self._seq_pending = use_rep
+        if (gpu and L.DENSE_ROUND and L.dense_fits(batch.dn, batch.dc, r.bias)
+                and batch.dn <= self.dim - 1 and r.rule in L.V3_RULES):
+            return Route("dense", *self._geometry(B, ctx), hashed=True)
+        R, S = self._geometry(B, ctx, active=True)
+        v3on = gpu and L.SEQ_KERNEL == "scan3"
+        if raw:
+            if v3on and B > 0 and L.scan3_eligible(batch, R, r.bias):
+                return Route("scan", R, S, hashed=False)
+            if self._plain():
+                return Route("seq", R, S, hashed=False)
+        elif (type(batch) is HashedBatch and v3on
+              and L.compact_scan_fits(batch, R, r.bias, self.dim, cbase=self.space.dn)):
+            return Route("scan", R, S, hashed=True)
+        return Route("table", *self._geometry(B, ctx), hashed=True)
+
+    def reduce_parts_apply(self, batch, ctx: RoundContext) -> bool:
+        """The spoke-table round reduces its tables in key-range parts and the dense round
+        reports them after its one launch; the scan and seq rounds complete the accumulator
+        only at their end (no part is final earlier): one reduce and one collective."""
+        return self.supports_reduce_parts and self.route(batch, ctx).kind in ("table", "dense")
+
+    def _routed(self, batch, ctx: RoundContext, rt: Route):
+        """``batch`` as the routed kernel reads it: hashed if raw, and spoke-padded (a
+        holdout-routed tick: spoke s trains exactly the rows spoke s routed)."""
+        if not rt.hashed:
+            return batch
+        if isinstance(batch, RawBatch):
+            batch = batch.hashed(self.space)
+        return batch.spoke_padded(max(1, int(ctx.spokes)))
+
+    def _set_clock(self) -> None:
+        self.rule.tbase = float(self.t0 + 1 + self.steps)  # Pegasos' step clock
+
+    def _idle_round(self, ctx: RoundContext) -> None:
+        """No rows on this rank this round: the model stays, the round counters are zero,
+        and every reduce part is still reported (the rank joins each collective)."""
+        self.dacc[self.dim:].zero_()
+        if ctx.on_reduce_part is not None:
+            parts = max(1, int(ctx.reduce_parts))
+            for k in range(parts):
+                ctx.on_reduce_part(k, *L.part_bounds(self.dim, k, parts, self.dacc.is_cuda))
+        self._seq_pending = False
         if not ctx.fused_delta:
             self.apply_delta()
 
-    # ------------------------------------------------------------ dense round
-    def _dense_eligible(self, batch) -> bool:
-        """A batch without categorical columns (hashed or raw) on a GPU trains through the
-        dense round (ops.linear.linear_dense_round)."""
-        return (L.DENSE_ROUND and self.w.is_cuda and batch.dc == 0
-                and L.dense_fits(batch.dn, batch.dc, self.rule.bias)
-                and batch.dn <= self.dim - 1 and self.rule.rule in L.V3_RULES)
+    def _replicas_for(self, S: int) -> torch.Tensor:
+        """The v1 round's [S, dim] replicas, equal to w."""
+        if self.replicas is None or self.replicas.shape[0] < S:
+            self.replicas = torch.empty((S, self.dim), dtype=torch.float32, device=self.device)
+            self._rep_valid = False
+        if not self._rep_valid:
+            L.linear_seq_broadcast(self.w, self.replicas)
+            self._rep_valid = True
+        return self.replicas
 
-    def _fit_dense(self, batch: HashedBatch, ctx: RoundContext) -> None:
-        B = batch.B
-        S = max(1, int(ctx.spokes))
-        R = max(1, -(-B // S)) if B else 1
+    def fit(self, batch, ctx: RoundContext) -> None:
+        rt = self.route(batch, ctx)
+        batch = self._routed(batch, ctx, rt)
+        if batch.B == 0:
+            return self._idle_round(ctx)
         parts = max(1, int(ctx.reduce_parts)) if ctx.on_reduce_part is not None else 1
-        if B:
-            self.rule.tbase = float(self.t0 + 1 + self.steps)
-            L.linear_dense_round(self._wread(), batch.contiguous(), R, S, self.dacc, self.rule,
-                                 ctx.inv_p, cum=self.cum, parts=parts,
-                                 on_part=ctx.on_reduce_part)
-            self.steps += R
+        w, R, S, on_part = self._wread(), rt.R, rt.S, ctx.on_reduce_part
+        # v3 (the table scan) keeps no dense replicas: its round end sums the spokes'
+        # updates from the sorted occurrence lists; v1 averages [S, dim] replicas
+        use_rep = rt.kind == "seq" and self.w.is_cuda
+        self._set_clock()
+        if rt.kind == "dense":
+            L.linear_dense_round(w, batch.contiguous(), R, S, self.dacc, self.rule, ctx.inv_p,
+                                 cum=self.cum, parts=parts, on_part=on_part)
+        elif rt.kind == "table":
+            L.linear_round(w, batch, R, S, self.dacc, None, self.rule, ctx.inv_p,
+                           self.log2cap, cum=self.cum, ablate=self.ablate, chunk=self.chunk,
+                           parts=parts, on_part=on_part)
         else:
-            self.dacc[self.dim:].zero_()  # no workers this round on this rank
-            if ctx.on_reduce_part is not None:  # still join every collective of the round
-                for k in range(parts):
-                    ctx.on_reduce_part(k, *L.part_bounds(self.dim, k, parts, self.dacc.is_cuda))
-        self._seq_pending = False
+            # a v3 prep made ahead for this batch (engine/job.py route stream, or the first
+            # pipeline of the tick that trains on it; ops.linear checks that it matches)
+            rb = L.compact_raw(batch, self.space.dn) if rt.hashed else batch
+            v3 = L.linear_seq_round(w, rb, R, S, self.dacc, self.rule, ctx.inv_p, cum=self.cum,
+                                    replicas=self._replicas_for(S) if use_rep else None,
+                                    parts=parts, on_part=on_part, hashed=rt.hashed)
+            assert v3 == (rt.kind == "scan"), "route and ops.linear_seq_round disagree"
+            if rt.hashed:
+                batch.prep = rb.prep
+        self.steps += R
+        self._seq_pending = use_rep
         if not ctx.fused_delta:
             self.apply_delta()
 
     # ------------------------------------------------------ several pipelines
     def group_key(self, batch, ctx: RoundContext):
         """Learners whose rounds on ``batch`` can share ONE launch: a key, or None when this
-        one cannot. Dense-eligible batches (no categorical column) group by dimension, rule
-        family, variant, bias, shrink mode and model dtype — C, ε, lr, λ and the Pegasos
-        clock may differ, there is no shared prep; the others by their v3 prep."""
-        if batch.B > 0 and self._dense_eligible(batch):
-            r = self.rule
+        one cannot. Dense rounds group by dimension, rule family, variant, bias, shrink mode
+        and model dtype — C, ε, lr, λ and the Pegasos clock may differ, there is no shared
+        prep; scan rounds by their v3 prep."""
+        kind = self.route(batch, ctx).kind if batch.B > 0 else None
+        r = self.rule
+        if kind == "dense":
             return ("dense", self.dim, r.rule, r.variant, bool(r.bias), L._s3_shrink(r)[0],
                     self.w16 is not None)
-        return self._scan_group_key(batch, ctx)
-
-    def _scan_group_key(self, batch, ctx: RoundContext):
-        """Learners whose rounds on ``batch`` can share ONE v3 launch (same prep, same rule
-        family and variant, no shrink, fp32): a key, or None when this one cannot."""
-        if not (self.w.is_cuda and self.seq_capable() and batch.B > 0):
+        if kind != "scan":
             return None
-        if isinstance(batch, RawBatch):
-            rb = batch
-            R, _ = self._seq_geometry(batch.B, ctx)
-            if not L.scan3_eligible(rb, R, self.rule.bias):
-                return None
-        else:
-            b = batch.spoke_padded(max(1, int(ctx.spokes)))
-            if not self._slots_scan_eligible(b, ctx):
-                return None
-        r = self.rule
-        r.tbase = float(self.t0 + 1 + self.steps)  # (Pegasos: the prep depends on the clock)
+        self._set_clock()  # (Pegasos: the prep depends on the clock)
         # (logistic: lr·y is folded into the prep's Gram columns, so only equal learning
         # rates share a prep — ops.linear._s3_key)
         return (self.dim, r.rule, r.variant, r.bias, r.C if r.variant == L.PA2 else None,
@@ -261,104 +273,53 @@ class LinearLearner(Learner):
     def prepare_ahead(self, batch: HashedBatch, ctx: RoundContext, stream) -> bool:
         """Make the v3 prep of this learner's round on ``batch`` now, on ``stream``, and
         attach it to the spoke-padded batch its ``fit`` will use (engine/job.py: the next
-        tick's route + prep run beside the current round). False: no v3 round here (the
-        dense round has no prep)."""
-        if self._scan_group_key(batch, ctx) is None:
+        tick's route + prep run beside the current round). False: no scan round on a hashed
+        batch here (the other rounds have no prep; a raw batch's is made by its round)."""
+        rt = self.route(batch, ctx)
+        if rt.kind != "scan" or not rt.hashed:
             return False
-        b = batch.spoke_padded(max(1, int(ctx.spokes)))
-        R, S = self._seq_geometry(b.B, ctx)
-        rb = RawBatch(b.num.float().contiguous(), b.cat.contiguous(), b.y.float().contiguous(),
-                      span=b.cat_span, cbase=self.space.dn)
-        key = L._s3_key(rb, R, S, self.dim, self.rule.bias, self.rule)
+        b = self._routed(batch, ctx, rt)
+        rb = L.compact_raw(b, self.space.dn)
+        self._set_clock()
+        key = L._s3_key(rb, rt.R, rt.S, self.dim, self.rule.bias, self.rule)
         if isinstance(b.prep, L.Scan3Prep) and b.prep.key == key:
             return True
-        b.prep = L.linear_scan3_prepare(rb, R, S, self.dim, bool(self.rule.bias), self.rule,
-                                        slot=L._s3_slot_for(key, self.w.device), stream=stream,
-                                        hashed=True)
+        b.prep = L.linear_scan3_prepare(rb, rt.R, rt.S, self.dim, bool(self.rule.bias),
+                                        self.rule, slot=L._s3_slot_for(key, self.w.device),
+                                        stream=stream, hashed=True)
         return True
 
     @staticmethod
     def fit_group(learners: list, batch, ctx: RoundContext) -> None:
         """One round of every learner in ``learners`` (equal ``group_key``) on ``batch`` in
         one launch (ops.linear.linear_scan3_round_multi, or linear_dense_round_multi for a
-        batch without categorical columns) — each learner ends exactly as its own ``fit``
-        would leave it."""
+        dense round) — each learner ends exactly as its own ``fit`` would leave it."""
         first = learners[0]
-        if first._dense_eligible(batch):
-            return LinearLearner._fit_group_dense(learners, batch, ctx)
-        hashed = False
-        if isinstance(batch, RawBatch):
-            rb = batch
-        else:
-            b = batch.spoke_padded(max(1, int(ctx.spokes)))
-            rb = RawBatch(b.num.float().contiguous(), b.cat.contiguous(), b.y.float().contiguous(),
-                          span=b.cat_span, cbase=first.space.dn)
-            rb.prep = getattr(b, "prep", None)
-            hashed = True
-        R, S = first._seq_geometry(rb.B, ctx)
+        rt = first.route(batch, ctx)
+        assert rt.kind in ("dense", "scan") and batch.B > 0, rt
+        batch = first._routed(batch, ctx, rt)
+        R, S = rt.R, rt.S
         for lr in learners:
-            lr.rule.tbase = float(lr.t0 + 1 + lr.steps)
-        step = L.scan3_max_pipes()
-        for i in range(0, len(learners), step):
-            grp = learners[i:i + step]
-            L.linear_scan3_round_multi([lr._wread() for lr in grp], rb, R, S,
-                                       [lr.dacc for lr in grp],
-                                       [lr.rule for lr in grp], ctx.inv_p,
-                                       [lr.cum for lr in grp], hashed=hashed)
-        if not isinstance(batch, RawBatch):
-            batch.prep = rb.prep
+            lr._set_clock()
+        ws, daccs = [lr._wread() for lr in learners], [lr.dacc for lr in learners]
+        rules, cums = [lr.rule for lr in learners], [lr.cum for lr in learners]
+        if rt.kind == "dense":
+            L.linear_dense_round_multi(ws, batch.contiguous(), R, S, daccs, rules, ctx.inv_p,
+                                       cums)
+        else:
+            rb = L.compact_raw(batch, first.space.dn) if rt.hashed else batch
+            step = L.scan3_max_pipes()
+            for i in range(0, len(learners), step):
+                j = i + step
+                L.linear_scan3_round_multi(ws[i:j], rb, R, S, daccs[i:j], rules[i:j],
+                                           ctx.inv_p, cums[i:j], hashed=rt.hashed)
+            if rt.hashed:
+                batch.prep = rb.prep
         for lr in learners:
             lr._seq_pending = False
             lr.steps += R
         if not ctx.fused_delta:  # the models averaged in one launch
             LinearLearner.apply_delta_group(learners)
-
-    @staticmethod
-    def _fit_group_dense(learners: list, batch, ctx: RoundContext) -> None:
-        if isinstance(batch, RawBatch):
-            batch = batch.hashed(learners[0].space)
-        b = batch.spoke_padded(max(1, int(ctx.spokes))).contiguous()
-        S = max(1, int(ctx.spokes))
-        R = max(1, -(-b.B // S)) if b.B else 1
-        for lr in learners:
-            lr.rule.tbase = float(lr.t0 + 1 + lr.steps)
-        L.linear_dense_round_multi([lr._wread() for lr in learners], b, R, S,
-                                   [lr.dacc for lr in learners], [lr.rule for lr in learners],
-                                   ctx.inv_p, [lr.cum for lr in learners])
-        for lr in learners:
-            lr._seq_pending = False
-            lr.steps += R
-        if not ctx.fused_delta:
-            LinearLearner.apply_delta_group(learners)
-
-    def fit(self, batch: HashedBatch, ctx: RoundContext) -> None:
-        if isinstance(batch, RawBatch):
-            if not self._dense_eligible(batch) and self.seq_capable(batch, ctx):
-                return self._fit_raw(batch, ctx)
-            batch = batch.hashed(self.space)
-        # a holdout-routed tick: spoke s trains exactly the rows spoke s routed
-        batch = batch.spoke_padded(max(1, int(ctx.spokes)))
-        if self._dense_eligible(batch):
-            return self._fit_dense(batch, ctx)
-        if self._slots_scan_eligible(batch, ctx):
-            return self._fit_slots(batch, ctx)
-        B = batch.B
-        S = max(1, int(ctx.spokes))
-        R = max(1, -(-B // S)) if B else 1
-        parts = max(1, int(ctx.reduce_parts)) if ctx.on_reduce_part is not None else 1
-        if B:
-            self.rule.tbase = float(self.t0 + 1 + self.steps)
-            L.linear_round(self._wread(), batch, R, S, self.dacc, None, self.rule, ctx.inv_p,
-                           self.log2cap, cum=self.cum, ablate=self.ablate, chunk=self.chunk,
-                           parts=parts, on_part=ctx.on_reduce_part)
-            self.steps += R
-        else:
-            self.dacc[self.dim:].zero_()  # no workers this round on this rank
-            if ctx.on_reduce_part is not None:  # still join every collective of the round
-                for k in range(parts):
-                    ctx.on_reduce_part(k, *L.part_bounds(self.dim, k, parts, self.dacc.is_cuda))
-        if not ctx.fused_delta:
-            self.apply_delta()
 
     def delta_buffer(self) -> torch.Tensor:
         return self.dacc

@@ -435,10 +435,7 @@ def multiclass_scan3_fits(batch, R: int, nclass: int, bias: bool, Wt) -> bool:
     from omldm_amd.ops import linear as L
 
     return (Wt is not None and Wt.is_cuda and Wt.dtype == torch.float32 and nclass <= _MC_SCAN_KMAX
-            and getattr(batch, "cat_span", 0) > 0 and batch.B > 0 and 0 < batch.dc
-            and L.SEQ_KERNEL == "scan3" and batch.y.is_cuda
-            and batch.dn + batch.dc * batch.cat_span <= int(Wt.shape[0]) - 1
-            and L.scan3_fits(batch.dn, batch.dc, R, bias))
+            and L.compact_scan_fits(batch, R, bias, int(Wt.shape[0])))
 
 
 def multiclass_scan3_round(Wt: torch.Tensor, batch, R: int, S: int, nclass: int, variant: int,
@@ -448,7 +445,6 @@ def multiclass_scan3_round(Wt: torch.Tensor, batch, R: int, S: int, nclass: int,
     workgroup per spoke carrying the K scores of each row through the chunk recurrence, then
     one scatter of the rows' ±τ into dacc [K, dim]. stats[0..3] += (loss, rows, mistakes,
     active spokes), like ``multiclass_round``."""
-    from omldm_amd.api.batch import RawBatch
     from omldm_amd.ops import linear as L
     from omldm_amd.ops.linear import _workspace
 
@@ -457,9 +453,8 @@ def multiclass_scan3_round(Wt: torch.Tensor, batch, R: int, S: int, nclass: int,
     kt = int(os.environ.get("OMLDM_MC_KT", "0") or 0)  # diagnostics: a wider template
     if kt in (4, 8, 16) and kt > K and kt <= int(Wt.shape[1]):
         K = kt
-    num = batch.num.float().contiguous()
     y = batch.y.float().contiguous() if batch.y.dtype != torch.int8 else batch.y.contiguous()
-    rb = RawBatch(num, batch.cat.contiguous(), y, span=batch.cat_span, cbase=batch.dn)
+    rb = L.compact_raw(batch, batch.dn, y)
     rule = L.LinearRule(rule=L.RULE_MULTI, variant=variant, C=C, bias=bias)
     key = L._s3_key(rb, R, S, dim, bias, rule)
     sp = getattr(batch, "prep", None)

@@ -515,10 +515,23 @@ def _s3_span(batch: RawBatch, dim: int) -> int:
     return int(batch.span) if batch.span > 0 else (dim - batch.dn - 1) // batch.dc
 
 
-def scan3_eligible_compact(batch: RawBatch, R: int, bias: bool, dim: int) -> bool:
-    """v3 on compact slots: the field ranges [cbase + f·span, …) must fit the model."""
-    return (scan3_eligible(batch, R, bias)
-            and batch.cbase + batch.dc * batch.span <= dim - 1)
+def compact_scan_fits(batch, R: int, bias: bool, dim: int, cbase: int | None = None) -> bool:
+    """The v3 scan takes this hashed batch as it is: field-aware compact int16 slots on the
+    GPU, rows and categorical columns, the field ranges [cbase + f·span, …) inside the model
+    (``cbase``: where they start, default the batch's dense width), a shape the prep takes."""
+    span = getattr(batch, "cat_span", 0)
+    cbase = batch.dn if cbase is None else cbase
+    return (span > 0 and SEQ_KERNEL == "scan3" and batch.B > 0 and 0 < batch.dc
+            and batch.y.is_cuda and cbase + batch.dc * span <= dim - 1
+            and scan3_fits(batch.dn, batch.dc, R, bias))
+
+
+def compact_raw(batch: HashedBatch, cbase: int, y: torch.Tensor | None = None) -> RawBatch:
+    """The compact wire the v3 scan reads, made from a field-aware hashed batch (its int16
+    slots as they are, ``y`` default its labels in fp32), carrying the batch's prep."""
+    y = batch.y.float() if y is None else y
+    return RawBatch(batch.num.float().contiguous(), batch.cat.contiguous(), y.contiguous(),
+                    getattr(batch, "prep", None), span=batch.cat_span, cbase=cbase)
 
 
 def _s3_mode(batch: RawBatch, hashed: bool) -> int:
@@ -845,7 +858,7 @@ def linear_seq_round(w: torch.Tensor, batch: RawBatch, R: int, S: int, dacc: tor
         linear_scan3_round(w, batch, R, S, dacc, rule, inv_p, cum, parts, on_part, hashed)
         return True
     # a shrinking rule (L2, Pegasos) or a bf16 model has no v1 / raw CPU form: the learner
-    # hashes the batch and takes the spoke-table round instead (models/linear.py: seq_capable)
+    # hashes the batch and takes the spoke-table round instead (models/linear.py: route)
     assert not shrinks(rule) and w.dtype == torch.float32, \
         "shrinking rules / bf16 models take the v3 scan or the spoke-table round"
     if on_part is not None:  # the other paths complete dacc in one go

@@ -7,7 +7,7 @@ only (a MultiClassPA behind a widening stage on a field-aware space trains and p
 with the widened base, and is left to one-row predicts): a field-aware (compact uint16)
 batch carries field-local categorical values, and the batched predict kernels place them at
 ``batch.dn + field·span`` — after a PolynomialFeatures stage that is the WIDENED dense
-width, while training (``LinearLearner._fit_slots``: ``cbase = space.dn``) and the serving
+width, while training (``LinearLearner.fit``'s scan round: ``cbase = space.dn``) and the serving
 plan keep the slots where the feature space put them. So for a widening pipeline over
 hashed slots the reference is taken on ``batch.to_wide()`` (absolute slots, made before
 the dense block widens), which is the rule of ``Pipeline.__init__``.

@@ -1,0 +1,210 @@
+"""``LinearLearner.route``: which kernel a linear round takes (dense, v3 scan, v1 / CPU
+oracle, spoke table), one row per line of the table in its docstring, and that ``fit``,
+``group_key``, ``reduce_parts_apply`` and ``prepare_ahead`` follow it. Rows that only ask
+for the route launch nothing."""
+import pytest
+import torch
+
+from omldm_amd.api.batch import FeatureSpace, HashedBatch, PolyBatch, RawBatch
+from omldm_amd.io.synthetic import synth_batch, synth_raw
+from omldm_amd.models.base import RoundContext
+from omldm_amd.models.linear import SVM, Route
+from omldm_amd.ops import linear as L
+
+gpu = pytest.mark.gpu
+DIM, SPOKES = 1 << 10, 4
+
+PLAIN = {"C": 0.5}
+LAM = {"C": 0.5, "lambda": 1e-3}
+PEGASOS = {"variant": "Pegasos"}
+BF16 = {"C": 0.5, "modelDtype": "bf16"}
+NOBIAS = {"C": 0.5, "bias": False}
+HYPERS = {"plain": PLAIN, "lam": LAM, "pegasos": PEGASOS, "bf16": BF16, "nobias": NOBIAS}
+
+# (form, dn, dc, field_aware, learner, patches, B, spokes) -> (kind on a GPU, R, S, hashed);
+# B = 250 at 4 spokes: R = 63, every spoke has rows; B = 9: R = 3 and the fourth spoke is
+# idle (dense / table keep it in S, scan / seq drop it)
+CASES = [
+    # raw, no categorical column: the dense round, whatever the learner
+    (("raw", 13, 0, False, "plain", (), 250, 4), ("dense", 63, 4, True)),
+    (("raw", 13, 0, False, "lam", (), 250, 4), ("dense", 63, 4, True)),
+    (("raw", 13, 0, False, "bf16", (), 9, 4), ("dense", 3, 4, True)),
+    (("raw", 13, 0, False, "plain", (), 0, 4), ("dense", 1, 4, True)),
+    # ... without it: v1 for the plain learner (no categorical column: not a v3 shape)
+    (("raw", 13, 0, False, "plain", ("nodense",), 250, 4), ("seq", 63, 4, False)),
+    (("raw", 13, 0, False, "lam", ("nodense",), 9, 4), ("table", 3, 4, True)),
+    # raw tokens: the v3 scan, every rule and model dtype
+    (("raw", 13, 2, False, "plain", (), 250, 4), ("scan", 63, 4, False)),
+    (("raw", 13, 2, False, "lam", (), 9, 4), ("scan", 3, 3, False)),
+    (("raw", 13, 2, False, "pegasos", (), 250, 4), ("scan", 63, 4, False)),
+    (("raw", 13, 2, False, "bf16", (), 250, 4), ("scan", 63, 4, False)),
+    # ... with the v1 kernel selected: plain learners only, the others hash
+    (("raw", 13, 2, False, "plain", ("v1",), 9, 4), ("seq", 3, 3, False)),
+    (("raw", 13, 2, False, "lam", ("v1",), 250, 4), ("table", 63, 4, True)),
+    (("raw", 13, 2, False, "pegasos", ("v1",), 250, 4), ("table", 63, 4, True)),
+    (("raw", 13, 2, False, "bf16", ("v1",), 250, 4), ("table", 63, 4, True)),
+    # ... of a shape outside the v3 scan: 33 fields, 8193 rows per spoke
+    (("raw", 13, 33, False, "plain", (), 250, 4), ("seq", 63, 4, False)),
+    (("raw", 13, 33, False, "lam", (), 250, 4), ("table", 63, 4, True)),
+    (("raw", 2, 2, False, "plain", (), 8193, 1), ("seq", 8193, 1, False)),
+    (("raw", 2, 2, False, "lam", (), 8193, 1), ("table", 8193, 1, True)),
+    (("raw", 2, 2, False, "lam", (), 8192, 1), ("scan", 8192, 1, False)),
+    # ... empty
+    (("raw", 13, 2, False, "plain", (), 0, 4), ("seq", 1, 4, False)),
+    (("raw", 13, 2, False, "lam", (), 0, 4), ("table", 1, 4, True)),
+    # hashed, no categorical column: dense up to 256 columns with the bias
+    (("hashed", 13, 0, False, "plain", (), 250, 4), ("dense", 63, 4, True)),
+    (("hashed", 13, 0, True, "pegasos", (), 9, 4), ("dense", 3, 4, True)),
+    (("hashed", 255, 0, False, "plain", (), 9, 4), ("dense", 3, 4, True)),
+    (("hashed", 256, 0, False, "plain", (), 9, 4), ("table", 3, 4, True)),
+    (("hashed", 256, 0, False, "nobias", (), 9, 4), ("dense", 3, 4, True)),
+    (("hashed", 13, 0, False, "plain", ("nodense",), 9, 4), ("table", 3, 4, True)),
+    # hashed field-aware slots: the v3 scan on the compact wire
+    (("hashed", 13, 2, True, "plain", (), 250, 4), ("scan", 63, 4, True)),
+    (("hashed", 13, 2, True, "lam", (), 9, 4), ("scan", 3, 3, True)),
+    (("hashed", 13, 2, True, "pegasos", (), 250, 4), ("scan", 63, 4, True)),
+    (("hashed", 13, 2, True, "bf16", (), 250, 4), ("scan", 63, 4, True)),
+    # ... everything else: the spoke-table round
+    (("hashed", 13, 2, False, "plain", (), 9, 4), ("table", 3, 4, True)),
+    (("poly", 13, 2, True, "plain", (), 250, 4), ("table", 63, 4, True)),
+    (("hashed", 13, 2, True, "plain", ("v1",), 250, 4), ("table", 63, 4, True)),
+    (("hashed", 13, 33, True, "plain", (), 250, 4), ("table", 63, 4, True)),
+    (("hashed", 2, 2, True, "plain", (), 8193, 1), ("table", 8193, 1, True)),
+    (("hashed", 13, 2, True, "plain", (), 0, 4), ("table", 1, 4, True)),
+]
+IDS = ["-".join(str(v) for v in (c[0][0], f"dn{c[0][1]}", f"dc{c[0][2]}", "fa" if c[0][3] else
+                                 "wide", c[0][4], *c[0][5], f"B{c[0][6]}")) for c in CASES]
+
+
+def blank(form, dn, dc, field_aware, B, device):
+    """A batch of the given form and shape (the route reads no values)."""
+    space = FeatureSpace(dn, 0, dc, DIM, field_aware=field_aware)
+    if form == "raw":
+        return space, RawBatch.empty(space, B, device=device)
+    b = HashedBatch.empty(space, B, device=device)
+    if form == "poly":
+        b = PolyBatch(b.num, b.cat, b.y, None, b.cat_span,
+                      torch.zeros((1, 2), dtype=torch.int32, device=device))
+    return space, b
+
+
+def routed(case, device, monkeypatch):
+    form, dn, dc, field_aware, learner, patches, B, spokes = case
+    if "nodense" in patches:
+        monkeypatch.setattr(L, "DENSE_ROUND", False)
+    if "v1" in patches:
+        monkeypatch.setattr(L, "SEQ_KERNEL", "seq")
+    space, batch = blank(form, dn, dc, field_aware, B, device)
+    lrn = SVM(HYPERS[learner], space, device)
+    return lrn, batch, lrn.route(batch, RoundContext(spokes=spokes))
+
+
+@pytest.mark.parametrize("case,want", CASES, ids=IDS)
+def test_route_cpu(case, want, monkeypatch):
+    """Without a GPU a raw batch of a plain learner takes the raw oracle and everything
+    else the spoke-table round's CPU form."""
+    lrn, batch, rt = routed(case, "cpu", monkeypatch)
+    B, spokes = case[6], case[7]
+    if case[0] == "raw" and case[4] in ("plain", "nobias"):
+        R = max(1, -(-B // spokes))
+        assert rt == Route("seq", R, -(-B // R) if B else spokes, False)
+    else:
+        assert rt == Route("table", max(1, -(-B // spokes)), spokes, True)
+    assert lrn.group_key(batch, RoundContext(spokes=spokes)) is None
+    assert lrn.reduce_parts_apply(batch, RoundContext(spokes=spokes)) == (rt.kind == "table")
+
+
+@gpu
+@pytest.mark.parametrize("case,want", CASES, ids=IDS)
+def test_route_gpu(case, want, cuda, monkeypatch):
+    lrn, batch, rt = routed(case, cuda, monkeypatch)
+    assert rt == Route(*want)
+    ctx = RoundContext(spokes=case[7])
+    key = lrn.group_key(batch, ctx)
+    if rt.kind in ("dense", "scan") and batch.B:
+        assert key is not None and (key[0] == "dense") == (rt.kind == "dense")
+    else:
+        assert key is None
+    assert lrn.reduce_parts_apply(batch, ctx) == (rt.kind in ("dense", "table"))
+
+
+def data(kind, device):
+    """A 250-row batch whose round on a GPU is of ``kind``."""
+    if kind == "seq":  # (with the v1 kernel selected)
+        space = FeatureSpace(13, 0, 2, DIM)
+        return space, synth_raw(space, 250, seed=7).to(device)
+    space = FeatureSpace(13, 0, 0 if kind == "dense" else 2, DIM, field_aware=kind == "scan")
+    return space, synth_batch(space, 250, seed=7).to(device)
+
+
+class Parts:
+    """A ``RoundContext`` that records the reduce parts reported to it."""
+
+    def __init__(self, fused=False):
+        self.calls = []
+        self.ctx = RoundContext(spokes=SPOKES, inv_p=1.0 / SPOKES, fused_delta=fused,
+                                reduce_parts=3,
+                                on_reduce_part=lambda k, lo, hi: self.calls.append((k, lo, hi)))
+
+
+@gpu
+@pytest.mark.parametrize("kind", ["dense", "scan", "seq", "table"])
+def test_fit_follows_the_route(kind, cuda, monkeypatch):
+    if kind == "seq":
+        monkeypatch.setattr(L, "SEQ_KERNEL", "seq")
+    space, batch = data(kind, cuda)
+    lrn = SVM(PLAIN, space, cuda)
+    rec = Parts()
+    assert lrn.route(batch, rec.ctx).kind == kind
+    key = lrn.group_key(batch, rec.ctx)
+    assert (key is None) == (kind in ("seq", "table"))
+    assert key is None or (key[0] == "dense") == (kind == "dense")
+    assert lrn.reduce_parts_apply(batch, rec.ctx) == (kind in ("dense", "table"))
+    assert lrn.prepare_ahead(batch, rec.ctx, torch.cuda.current_stream(cuda)) == (kind == "scan")
+    prep = batch.prep
+    assert isinstance(prep, L.Scan3Prep) == (kind == "scan")
+    dense, scan = L.DENSE_ROUNDS, L.SCAN3_ROUNDS
+    lrn.fit(batch, rec.ctx)
+    torch.cuda.synchronize()
+    assert L.DENSE_ROUNDS - dense == (kind == "dense")
+    assert L.SCAN3_ROUNDS - scan == (kind == "scan")
+    assert (lrn.replicas is not None) == (kind == "seq")  # v1's [S, dim] replicas
+    assert batch.prep is prep  # the prep made ahead was the round's
+    if kind == "scan":
+        want = [(k, *L.scan3_part_bounds(DIM, batch.dn, batch.dc, k, 3, batch.cat_span))
+                for k in range(3)]
+    else:
+        want = [(k, *L.part_bounds(DIM, k, 3, True)) for k in range(3)]
+    assert rec.calls == want
+    assert float(lrn.cum[1]) == batch.B and bool((lrn.w != 0).any())
+    assert float(lrn.dacc[:DIM].abs().sum()) == 0  # applied: the accumulator is clear again
+
+
+def idle_round(form, dc, device):
+    space, batch = blank(form, 13, dc, False, 0, device)
+    lrn = SVM(PLAIN, space, device)
+    lrn.w.copy_(torch.randn(DIM, generator=torch.Generator().manual_seed(3)))
+    w0 = lrn.w.clone()
+    lrn.dacc[DIM:] = 5.0  # (a stale count must not survive the round)
+    rec = Parts(fused=True)
+    kind = lrn.route(batch, rec.ctx).kind
+    lrn.fit(batch, rec.ctx)
+    assert float(lrn.dacc[DIM:].abs().sum()) == 0
+    assert rec.calls == [(k, *L.part_bounds(DIM, k, 3, lrn.w.is_cuda)) for k in range(3)]
+    lrn.apply_delta()
+    assert torch.equal(lrn.w, w0) and lrn.steps == 0
+    assert lrn.replicas is None  # an empty v1 round broadcasts no replicas
+    return kind
+
+
+@pytest.mark.parametrize("form,dc,kind", [("raw", 2, "seq"), ("hashed", 2, "table"),
+                                          ("hashed", 0, "table")])
+def test_empty_round_cpu(form, dc, kind):
+    assert idle_round(form, dc, "cpu") == kind
+
+
+@gpu
+@pytest.mark.parametrize("form,dc,kind", [("raw", 2, "seq"), ("hashed", 2, "table"),
+                                          ("hashed", 0, "dense"), ("raw", 0, "dense")])
+def test_empty_round_gpu(form, dc, kind, cuda):
+    assert idle_round(form, dc, cuda) == kind

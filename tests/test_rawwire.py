@@ -310,8 +310,9 @@ def test_gpu_engine_field_aware_batches_take_the_scan_round():
     res = {}
     for dev in ("cpu", "cuda"):
         lrn = SVM({"variant": "PA-I", "C": 1.0}, space, dev)
-        assert dev == "cpu" or lrn._slots_scan_eligible(synth_batch(space, 64).to(dev))
         proto = Synchronous(Comm(), lrn, {"virtualSpokes": 16})
+        assert dev == "cpu" or lrn.route(synth_batch(space, 64).to(dev),
+                                         proto._ctx(fused=True)).kind == "scan"
         for k in range(4):
             b = synth_batch(space, 16 * 500, start=k * 16 * 500, seed=25)
             assert type(b) is HashedBatch and b.cat_span > 0
