@@ -346,7 +346,7 @@ OMLDM_HOST_API int64_t omldm_fill_regions(int nj, const int64_t* jobs, uint8_t* 
     for (auto& x : th) x.join();
   } else {
     const int ntr = nt > nj ? nj : nt;
-    // measured (scripts/gpu_r4_pool.sh, same box, alternated): a thread per reader per
+    // measured (same box, alternated): a thread per reader per
     // block 149-150 M DIB records/s end to end, the pool 111-112 M (its workers'
     // condition-variable wake-ups and the shared job counter cost more than thread
     // creation): the pool is opt-in

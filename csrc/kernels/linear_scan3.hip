@@ -49,9 +49,6 @@
 #include "hash_dev.h"
 #include "seq_common.h"
 
-#include <mutex>
-#include <unordered_map>
-
 namespace omldm {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -413,10 +410,6 @@ __global__ __launch_bounds__(256) void s3_gram_kernel(const int* __restrict__ sl
   }
 }
 
-// Diagnostics: bit 0 skips the categorical match counts, bit 1 the dense MFMA, bit 2 the
-// output stores of s3_gram_mfma_kernel (scripts/gram_ablate.py; 0 in production)
-__device__ int g_s3_gram_ablate = 0;
-
 // Pass 3 on the matrix cores (the default; s3_gram_kernel above is the VALU reference the
 // GPU test compares it with). grid (chunks, S_act), 256 threads = 4 waves. Every load of the
 // chunk pair (slots of chunks c and c − 1, their numerical rows) is issued before the first
@@ -523,12 +516,11 @@ __global__ __launch_bounds__(256) void s3_gram_mfma_kernel(const int* __restrict
     f32x16 acc;
 #pragma unroll
     for (int g = 0; g < 16; ++g) acc[g] = 0.f;
-    const int abl = g_s3_gram_ablate;
     if (!zero) {
       int cnt[16];
 #pragma unroll
       for (int g = 0; g < 16; ++g) cnt[g] = 0;
-      for (int f = 0; f < ((abl & 1) ? 0 : dc); ++f) {
+      for (int f = 0; f < dc; ++f) {
         const int b = sl[d][f][J0 + l31];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -544,14 +536,11 @@ __global__ __launch_bounds__(256) void s3_gram_mfma_kernel(const int* __restrict
       }
 #pragma unroll
       for (int g = 0; g < 16; ++g) acc[g] = (float)cnt[g];
-      if (!(abl & 2)) {
 #pragma unroll
-        for (int k0 = 0; k0 < KN; k0 += 2)
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xn[0][I0 + l31][k0 + hi],
-                                                     xn[d][J0 + l31][k0 + hi], acc, 0, 0, 0);
-      }
+      for (int k0 = 0; k0 < KN; k0 += 2)
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xn[0][I0 + l31][k0 + hi],
+                                                   xn[d][J0 + l31][k0 + hi], acc, 0, 0, 0);
     }
-    if (abl & 4) continue;
 #pragma unroll
     for (int g = 0; g < 16; ++g) {
       const int t = I0 + (g & 3) + 8 * (g >> 2) + 4 * hi, col = J0 + l31;
@@ -633,11 +622,9 @@ struct S3Cand {
 };
 
 __device__ unsigned long long* g_s3_stamps;
-__device__ int g_s3_debug;  // diagnostics: 1 = every gather reads w[0] (latency experiment)
+__device__ int g_s3_stamp_wave = 1;  // the helper wave whose phases are stamped
 __device__ unsigned long long* g_s3mc_dbg;  // MultiClassPA scan phase cycles (null: off)
 __device__ int g_s3_comb_err;  // a combiner gave up waiting for its spoke (bounded spin)
-__device__ int g_s3_dense_order = 0;  // helpers' dense column ownership (see s3_scan_kernel)
-__device__ int g_s3_hprio = 0;         // helpers' issue priorities by age (A/B: see s3_scan_body)
 
 // The in-launch combine (Guideline 16, R2 "the data is the flag"): the scanner stores row
 // t's c as one 8-B granule {epoch << 32 | bits(c)} with a relaxed agent-scope atomic store
@@ -664,7 +651,6 @@ struct S3Comb {
   double* cum;
   const float* sig;  // shrinking rules: σ at each spoke's end (its c's scale), else null
   int wbf;           // the model w is bf16 (modelDtype bf16: margins on the bf16 weights)
-  int cns;           // spokes per combiner workgroup (> 1: one part, chunks interleaved)
   // in-scan combine (no combiner workgroups): the helpers add every table occurrence's
   // c·sign to the table and the scan workgroup flushes it through l2s ([S][gs]: each table
   // id's slot) at its end; a non-table occurrence's (F_PRES) goes to dacc from the helpers
@@ -675,9 +661,8 @@ struct S3Comb {
 };
 
 // workgroups of one pipeline: its w0-margin (RARE) and scan workgroups, then its combiners
-__host__ __device__ inline int s3_nper(int S_act, bool rare, int ncomb, int cns) {
-  const int nc = cns > 1 ? (S_act + cns - 1) / cns : ncomb * S_act;
-  return S_act * (rare ? 2 : 1) + (ncomb > 0 ? nc : 0);
+__host__ __device__ inline int s3_nper(int S_act, bool rare, int ncomb) {
+  return S_act * (rare ? 2 : 1) + (ncomb > 0 ? ncomb * S_act : 0);
 }
 
 // w[i] of a bf16 model (wbf) or an fp32 one
@@ -695,12 +680,9 @@ constexpr unsigned SPIN_MAX = 1u << 21;      // polls before a combiner gives up
 // the scanner and only the last chunk is left when the scan ends (one wave per field, every
 // chunk, fell behind: its slot loads and its poll were one round trip each per chunk). All
 // of a chunk's slot loads are issued before the poll. Rows with c = 0 add nothing.
-// ns > 1: one combiner for spokes s .. s + ns − 1, their chunks interleaved in time order
-// (chunk k of each spoke in turn: the spokes scan at the same pace) — fewer workgroups when
-// a launch holds more pipelines than the GPU has CUs.
 __device__ __forceinline__ void s3_combine_spoke(const int* __restrict__ slotsT, int dc, int B,
                                                  int R, const S3Comb& cb, S3Smem& sm, int s,
-                                                 int part, int nparts, int ns = 1) {
+                                                 int part, int nparts) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int* hk = reinterpret_cast<int*>(&sm.G[0][0][0]);
   float* hv = &sm.X1[0][0][0];
@@ -712,13 +694,11 @@ __device__ __forceinline__ void s3_combine_spoke(const int* __restrict__ slotsT,
   const int nchs = (R + s3::CH - 1) / s3::CH;  // chunks of a full spoke
   const int wstride = nparts * (s3::NH + 1);
   const unsigned long long want = (unsigned long long)cb.epoch;
-  for (int kk = part * (s3::NH + 1) + wave; kk < nchs * ns; kk += wstride) {
-    const int si = s + kk % ns, k = kk / ns;
-    if (si >= cb.S_act) continue;
-    int t0, t1;
-    spoke_rows(si, R, B, t0, t1);
-    // σ_end·Σ c·x: the spoke's Δ
-    const float sc = cb.inv_p * (cb.sig ? cb.sig[si] : 1.f);
+  int t0, t1;
+  spoke_rows(s, R, B, t0, t1);
+  // σ_end·Σ c·x: the spoke's Δ
+  const float sc = cb.inv_p * (cb.sig ? cb.sig[s] : 1.f);
+  for (int k = part * (s3::NH + 1) + wave; k < nchs; k += wstride) {
     const int row = t0 + k * s3::CH + lane;
     const bool in = row < t1;
     int v[s3::MAXF];
@@ -896,16 +876,11 @@ __device__ __forceinline__ void s3_fold_pres(const uint32_t* __restrict__ meta, 
   }
 }
 
-// A combiner workgroup: ns = 1: spoke i mod S_act, part i / S_act of the combiner blocks;
-// ns > 1 (one part): spokes ns·i .. ns·i + ns − 1.
+// A combiner workgroup: spoke i mod S_act, part i / S_act of the combiner blocks.
 __device__ __forceinline__ void s3_combine(const int* __restrict__ slotsT, int dc, int B, int R,
                                            const S3Comb& cb, S3Smem& sm, int base, int bid,
-                                           int nblk, int ns) {
+                                           int nblk) {
   const int i = bid - base;
-  if (ns > 1) {
-    s3_combine_spoke(slotsT, dc, B, R, cb, sm, ns * i, 0, 1, ns);
-    return;
-  }
   s3_combine_spoke(slotsT, dc, B, R, cb, sm, i % cb.S_act, i / cb.S_act, (nblk - base) / cb.S_act);
 }
 
@@ -1005,25 +980,9 @@ __device__ __forceinline__ void s3_inscan_flush(const S3Comb& cb, const float* t
 // from its granule (rgran), the helpers gather only the table slots' first occurrences.
 // One pipeline's workgroup `bid` of the round (`nblk` per pipeline): [0, S_act) the scan
 // workgroups, [S_act, 2·S_act) the rare-slot ones (RARE), then the combiners.
-// End of a scan workgroup with rows (every wave): with `tail` (a launch too large for
-// in-launch combiners) the workgroup folds its own spoke's c·sign into the accumulator now
-// that its scan is done (s3_combine_spoke over its LDS, free after the last chunk), then
-// the arrival / round tail.
-__device__ __forceinline__ void s3_spoke_end(bool tail, const int* __restrict__ slotsT, int dc,
-                                             int B, int R, const S3Comb& cb,
-                                             const float* __restrict__ ws,
-                                             const float* __restrict__ wsd, int dn, int dim,
-                                             const SeqParams& p, S3Smem& sm, int s) {
-  if (tail) {
-    __syncthreads();  // the scanner is done with G / X1
-    s3_combine_spoke(slotsT, dc, B, R, cb, sm, s, 0, 1);
-  }
-  s3_scan_arrive(cb, ws, wsd, dn, dim, p, sm);
-}
-
 template <int RULE, int KN, bool RARE>
 __device__ __forceinline__ void s3_scan_body(
-    int bid, int nblk, int tail, S3Smem& sm, float* tab,
+    int bid, int nblk, S3Smem& sm, float* tab,
     const int* __restrict__ slotsT, const uint32_t* __restrict__ meta, int dc, int dn,
     const void* __restrict__ yv, int B, int R, const float* __restrict__ prep, int nchs,
     const float* __restrict__ w, int dim, float* __restrict__ aglob, int cap, long long gstride,
@@ -1034,13 +993,9 @@ __device__ __forceinline__ void s3_scan_body(
     if (RARE && bid < 2 * cb.S_act) {  // a rare-slot workgroup
       s3_rare(slotsT, dc, B, R, w, cb, rgran, sm, bid - cb.S_act);
       if (cb.inscan == 2) s3_fold_pres(meta, dc, B, R, cb, bid - cb.S_act);
-      if (tail == 2) {  // then the spoke's combiner: its w0 pass ends long before the scan
-        __syncthreads();
-        s3_combine_spoke(slotsT, dc, B, R, cb, sm, bid - cb.S_act, 0, 1);
-      }
       return;
     }
-    s3_combine(slotsT, dc, B, R, cb, sm, (RARE ? 2 : 1) * cb.S_act, bid, nblk, cb.cns);
+    s3_combine(slotsT, dc, B, R, cb, sm, (RARE ? 2 : 1) * cb.S_act, bid, nblk);
     return;
   }
   const int tid = threadIdx.x;
@@ -1060,7 +1015,6 @@ __device__ __forceinline__ void s3_scan_body(
   float* ag = aglob + (size_t)s * gstride;
 
   unsigned long long* stamps = g_s3_stamps;
-  const bool dbg_gather = g_s3_debug == 1;
   unsigned long long st_acc[12] = {};
   unsigned long long st_t = stamps ? clock64() : 0;
   auto stamp = [&](int k) {
@@ -1209,27 +1163,14 @@ __device__ __forceinline__ void s3_scan_body(
       wr[7] = 0.f;
     }
     if (cb.inscan) s3_inscan_flush<RARE>(cb, tab, ag, cap, w, s);
-    s3_spoke_end(tail == 1, slotsT, dc, B, R, cb, ws, wsd, dn, dim, p, sm, s);
+    s3_scan_arrive(cb, ws, wsd, dn, dim, p, sm);
     return;
   }
 
   // ------------------------------------------------------------------- helpers
   // helper q owns categorical fields f ≡ q and dense columns j ≡ q (mod NHA); lane r = row
   const int q = wave - 1, r = lane;
-  const int swave = g_s3_debug >= 16 ? g_s3_debug - 16 : 1;  // the stamped helper wave
-  // A/B (off): issue priority by age on each SIMD. With equal priorities the oldest wave
-  // issues first and the youngest helpers (waves 8-11) set the chunk period; lifting them
-  // moves the starvation to the oldest (profiles/round5/probe_helpers_prio.txt: 0.263-0.266
-  // vs 0.270-0.274 ms) — the helpers share the SIMDs' issue slots, so only fewer helper
-  // instructions shorten the period
-  if (g_s3_hprio) {
-    if (q >= 7) __builtin_amdgcn_s_setprio(2);
-    else if (q >= 3) __builtin_amdgcn_s_setprio(1);
-  }
-  // dense column ownership: j ≡ q (mod NHA) (order 0), or in the reverse order of the
-  // fields (order 1: the helpers that own a third categorical field do not also own a
-  // second dense column)
-  const int qd = g_s3_dense_order ? s3::NHA - 1 - q : q;
+  const int swave = g_s3_stamp_wave;  // the stamped helper wave (omldm_scan3_stamps)
   const int kd = dn + (p.bias ? 1 : 0);  // real dense columns (KN pads them to 16 / 32)
   const int hl = q * 64 + lane;
   const bool inscan = cb.inscan != 0, inscan1 = cb.inscan == 1;  // 2: s3_fold_pres
@@ -1238,7 +1179,7 @@ __device__ __forceinline__ void s3_scan_body(
   float wn[s3::NJ], w0[s3::NJ];  // running dense weights of this wave's columns, round start
 #pragma unroll
   for (int i = 0; i < s3::NJ; ++i) {
-    const int j = qd + s3::NHA * i;
+    const int j = q + s3::NHA * i;
     const int jw = j < dn ? j : dim - 1;
     const float wj = cb.wbf ? s3_w16(w, jw) : w[jw];
     w0[i] = (j < KN && (j < dn || (p.bias && j == dn))) ? wj : 0.f;
@@ -1309,7 +1250,7 @@ __device__ __forceinline__ void s3_scan_body(
 #pragma unroll
       for (int i = 0; i < s3::NF; ++i) {
         const bool glob = !RARE && S.cs[i] != -1 && !(S.cm[i] & s3::F_TG);
-        S.g[i] = s3_w16(w, (glob && !dbg_gather) ? (S.cs[i] & 0x7fffffff) : 0);
+        S.g[i] = s3_w16(w, glob ? (S.cs[i] & 0x7fffffff) : 0);
       }
       return;
     }
@@ -1317,7 +1258,7 @@ __device__ __forceinline__ void s3_scan_body(
     for (int i = 0; i < s3::NF; ++i) {
       // RARE: no gathers here (s3_rare sums every occurrence's w0)
       const bool glob = !RARE && S.cs[i] != -1 && !(S.cm[i] & s3::F_TG);
-      S.g[i] = w[(glob && !dbg_gather) ? (S.cs[i] & 0x7fffffff) : 0];  // unused unless glob
+      S.g[i] = w[glob ? (S.cs[i] & 0x7fffffff) : 0];  // unused unless glob
     }
   };
   // aG_{ch} and aX1_{ch+1} (clamped reads past the round: never stored)
@@ -1335,7 +1276,7 @@ __device__ __forceinline__ void s3_scan_body(
   auto load_dense = [&](int ch, float* xd) {
 #pragma unroll
     for (int i = 0; i < NJK; ++i) {
-      const int j = qd + s3::NHA * i;
+      const int j = q + s3::NHA * i;
       const bool ok = j < KN && ch >= 0 && ch < nch;
       const int jc = j < KN ? j : 0, cc = max(0, min(ch, nch - 1));
       const float v = chunk_prep(cc)[2 * s3::MAT + s3::CH + jc * s3::CH + r];
@@ -1386,7 +1327,7 @@ __device__ __forceinline__ void s3_scan_body(
       }
 #pragma unroll
       for (int i = 0; i < NJK; ++i) {
-        const int j = qd + s3::NHA * i;
+        const int j = q + s3::NHA * i;
         if (j < kd) wn[i] += wave_sum(cv * CUR.xs[i]);  // (padding columns are all zero)
       }
     }
@@ -1511,12 +1452,12 @@ __device__ __forceinline__ void s3_scan_body(
   // round end: this wave's dense deltas
 #pragma unroll
   for (int i = 0; i < s3::NJ; ++i) {
-    const int j = qd + s3::NHA * i;
+    const int j = q + s3::NHA * i;
     if (lane == 0 && j < KN) wsd[(size_t)s * s3::DS + j] = wn[i] - w0[i];
   }
   if (q == 0 && lane >= KN && lane < s3::DS) wsd[(size_t)s * s3::DS + lane] = 0.f;
   if (cb.inscan) s3_inscan_flush<RARE>(cb, tab, ag, cap, w, s);
-  s3_spoke_end(tail == 1, slotsT, dc, B, R, cb, ws, wsd, dn, dim, p, sm, s);
+  s3_scan_arrive(cb, ws, wsd, dn, dim, p, sm);
 }
 
 // Several pipelines that share one prep (the same batch and row scaling: BASELINE config 5's
@@ -1540,8 +1481,6 @@ struct S3Pipe {
 struct S3Pipes {
   int M;
   int ncomb;  // combiner workgroups per spoke (0: none)
-  int tail;   // 1: each scan workgroup combines its own spoke after its scan; 2: the
-              // spoke's w0-margin workgroup combines it once its w0 pass is done (RARE)
   // the prep made on another stream: every workgroup waits for its ready word to reach
   // `wepoch` (omldm_scan3_signal at the prep's end) instead of the launch waiting on the
   // prep's event (null: no wait)
@@ -1586,7 +1525,7 @@ __global__ __launch_bounds__(s3::NT, s3::WPE) __attribute__((amdgpu_waves_per_eu
     int dim, int cap, long long gstride, int S_act, S3Pipes pp) {
   __shared__ S3Smem sm;
   extern __shared__ float tab[];  // [cap] + 64 scratch words (one per lane)
-  const int nblk = s3_nper(S_act, RARE, pp.ncomb, pp.pipe[0].cb.cns);  // per pipeline
+  const int nblk = s3_nper(S_act, RARE, pp.ncomb);  // per pipeline
   const int pi = (int)blockIdx.x / nblk, local = (int)blockIdx.x % nblk;
   s3_wait_prep(pp.wflag, pp.wepoch);
   int bid;
@@ -1594,9 +1533,8 @@ __global__ __launch_bounds__(s3::NT, s3::WPE) __attribute__((amdgpu_waves_per_eu
   else if (RARE && local < 2 * S_act) bid = local - S_act;
   else bid = local;  // (!RARE: scan blocks [0, S_act), combiners after)
   const S3Pipe& P = pp.pipe[pi];
-  s3_scan_body<RULE, KN, RARE>(bid, nblk, pp.tail, sm, tab, slotsT, meta,
-                               dc, dn, yv, B, R, prep, nchs, P.w, dim, P.aglob, cap, gstride,
-                               P.cb, P.ws, P.wsd, P.p, P.rgran);
+  s3_scan_body<RULE, KN, RARE>(bid, nblk, sm, tab, slotsT, meta, dc, dn, yv, B, R, prep, nchs,
+                               P.w, dim, P.aglob, cap, gstride, P.cb, P.ws, P.wsd, P.p, P.rgran);
 }
 
 // ------------------------------------------------------------------ pass 5: combine
@@ -2325,7 +2263,7 @@ static int s3_launch_scan_t(const int* slotsT, const uint32_t* meta, int dc, int
   }
   // per pipeline: S_act rare-slot (RARE), S_act scan and ncomb·S_act combiner workgroups,
   // role-major across the pipelines (s3_scan_kernel)
-  const int nblk = pp.M * s3_nper(S_act, RARE, pp.ncomb, pp.pipe[0].cb.cns);
+  const int nblk = pp.M * s3_nper(S_act, RARE, pp.ncomb);
   hipLaunchKernelGGL((s3_scan_kernel<RULE, KN, RARE>), dim3(nblk), dim3(s3::NT),
                      (size_t)(cap + 64) * sizeof(float), st, slotsT, meta, dc, dn, y, B, R, prep,
                      nchs, dim, cap, gstride, S_act, pp);
@@ -2393,23 +2331,11 @@ OMLDM_API void omldm_scan3_set_cap(int cap) { g_s3_cap_override = cap; }
 // 1: pass 3 on the VALU reference kernel (tests: A/B against the MFMA kernel)
 static int g_s3_gram_valu = 0;
 OMLDM_API void omldm_scan3_set_gram_valu(int v) { g_s3_gram_valu = v; }
-OMLDM_API int omldm_scan3_set_gram_ablate(int v) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_s3_gram_ablate), &v, sizeof(v));
-}
 
 // combiner workgroups per spoke in the scan's launch (0: the whole-GPU scatter kernel after
 // the scan — the A/B reference); at most (MAXF + 11) / 12 parts do work
 static int g_s3_comb = 1;
 OMLDM_API void omldm_scan3_set_comb(int v) { g_s3_comb = v < 0 ? 0 : (v > 3 ? 3 : v); }
-// launch form of a mode-4 round: 0 / 1 the latency form (pipelines beyond the GPU's CUs run
-// in later waves of workgroups: the pipeline-major block order needs no co-residency), 2 the
-// throughput form (one self-contained workgroup per spoke, helpers gather),
-// 3 w0-margin workgroups with each scan workgroup combining its own spoke (no combiners),
-// 4 two workgroups per spoke: the w0-margin workgroup combines the spoke after its w0 pass
-static int g_s3_form = 0;
-static int g_s3_cns = 0;  // spokes per combiner workgroup: 0 auto
-OMLDM_API void omldm_scan3_set_cns(int v) { g_s3_cns = v < 0 || v > 16 ? 0 : v; }
-OMLDM_API void omldm_scan3_set_form(int v) { g_s3_form = v < 0 || v > 4 ? 0 : v; }
 OMLDM_API int omldm_scan3_get_comb() { return g_s3_comb; }
 
 // 1 if a combiner gave up waiting for its spoke's granules since the last call (resets it;
@@ -2466,8 +2392,6 @@ OMLDM_API long long omldm_scan3_ws_words(int which, int B, int R, int S, int dn,
   return 0;
 }
 
-OMLDM_API int omldm_scan3_nbufs() { return 8; }
-
 struct S3Ws {
   int* slotsT;
   uint32_t* meta;
@@ -2482,52 +2406,6 @@ struct S3Ws {
 static S3Ws s3_ws(void* const* ptrs) {
   return S3Ws{(int*)ptrs[0], (uint32_t*)ptrs[1], (int*)ptrs[2], (float*)ptrs[3],
               (unsigned long long*)ptrs[4], (float*)ptrs[5], (float*)ptrs[6], (float*)ptrs[7]};
-}
-
-// The Gram pass needs the slots but not the flags: it runs on a companion stream of the
-// caller's (same CU mask) beside the flags pass, and the caller's stream waits for both.
-static int g_s3_prep_split = 0;  // measured: 309.5 (on) vs 319.8 M ex/s (off)
-OMLDM_API void omldm_scan3_set_prep_split(int v) { g_s3_prep_split = v; }
-namespace {
-struct S3Side {
-  hipStream_t side;
-  hipEvent_t fork, join;
-};
-std::mutex g_s3_side_mu;
-std::unordered_map<hipStream_t, S3Side> g_s3_side;
-
-S3Side* s3_side(hipStream_t st) {
-  std::lock_guard<std::mutex> lk(g_s3_side_mu);
-  auto it = g_s3_side.find(st);
-  if (it != g_s3_side.end()) return &it->second;
-  S3Side sd{};
-  uint32_t mask[32] = {};
-  const bool masked = st != nullptr && hipExtStreamGetCUMask(st, 32, mask) == hipSuccess;
-  if (!(masked && hipExtStreamCreateWithCUMask(&sd.side, 32, mask) == hipSuccess) &&
-      hipStreamCreateWithFlags(&sd.side, hipStreamNonBlocking) != hipSuccess)
-    return nullptr;
-  if (hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&sd.join, hipEventDisableTiming) != hipSuccess)
-    return nullptr;
-  return &g_s3_side.emplace(st, sd).first->second;
-}
-}  // namespace
-
-// Explicit teardown of the HIP objects this library created on demand (the companion prep
-// streams and their fork / join events): called from the Python loader's atexit hook, while
-// the HIP runtime is still up — not left to static destructors at process exit.
-OMLDM_API int omldm_scan3_teardown() {
-  std::lock_guard<std::mutex> lk(g_s3_side_mu);
-  int n = 0;
-  for (auto& kv : g_s3_side) {
-    hipStreamSynchronize(kv.second.side);
-    hipEventDestroy(kv.second.fork);
-    hipEventDestroy(kv.second.join);
-    hipStreamDestroy(kv.second.side);
-    ++n;
-  }
-  g_s3_side.clear();
-  return n;
 }
 
 // Passes 1-3 (model-independent): slots, flags, Grams. `src` is the tokens (hashed = 0),
@@ -2551,13 +2429,6 @@ OMLDM_API int omldm_scan3_prepare(const float* num, int dn, const void* src, int
   hipLaunchKernelGGL(s3_slots_kernel, dim3((B + 255) / 256), dim3(256), 0, st, src, B, dc, dn,
                      span, hashed, cbase, W.slotsT);
   hipMemsetAsync(W.lidcount, 0, sizeof(int) * S, st);
-  S3Side* sd = g_s3_prep_split ? s3_side(st) : nullptr;
-  hipStream_t gst = st;  // the Gram pass's stream
-  if (sd) {
-    hipEventRecord(sd->fork, st);
-    hipStreamWaitEvent(sd->side, sd->fork, 0);
-    gst = sd->side;
-  }
   hipLaunchKernelGGL(s3_flags_kernel, dim3(dc, S_act), dim3(s3::FT), 0, st, W.slotsT, B, R,
                      W.meta, W.lidcount, dim <= (1 << 22) ? 1 : 0,
                      reinterpret_cast<int*>(W.meta + (size_t)dc * B),
@@ -2572,31 +2443,27 @@ OMLDM_API int omldm_scan3_prepare(const float* num, int dn, const void* src, int
   const float cscale = rule == kSeqLogistic && !shr ? lr : 0.f;
   if (g_s3_gram_valu) {
     if (s3_kn(dn, bias) == 16)
-      hipLaunchKernelGGL(s3_gram_kernel<16>, dim3(nchs, S_act), dim3(256), 0, gst, W.slotsT, dc,
+      hipLaunchKernelGGL(s3_gram_kernel<16>, dim3(nchs, S_act), dim3(256), 0, st, W.slotsT, dc,
                          num, dn, y, y8, B, R, bias, affine, kadd, W.prep, nchs, shr, shr_r, cscale);
     else
-      hipLaunchKernelGGL(s3_gram_kernel<32>, dim3(nchs, S_act), dim3(256), 0, gst, W.slotsT, dc,
+      hipLaunchKernelGGL(s3_gram_kernel<32>, dim3(nchs, S_act), dim3(256), 0, st, W.slotsT, dc,
                          num, dn, y, y8, B, R, bias, affine, kadd, W.prep, nchs, shr, shr_r, cscale);
   } else if (s3_kn(dn, bias) == 16) {
-    hipLaunchKernelGGL(s3_gram_mfma_kernel<16>, dim3(nchs, S_act), dim3(256), 0, gst, W.slotsT,
+    hipLaunchKernelGGL(s3_gram_mfma_kernel<16>, dim3(nchs, S_act), dim3(256), 0, st, W.slotsT,
                        dc, num, dn, y, y8, B, R, bias, affine, kadd, W.prep, nchs, shr, shr_r, cscale);
   } else {
-    hipLaunchKernelGGL(s3_gram_mfma_kernel<32>, dim3(nchs, S_act), dim3(256), 0, gst, W.slotsT,
+    hipLaunchKernelGGL(s3_gram_mfma_kernel<32>, dim3(nchs, S_act), dim3(256), 0, st, W.slotsT,
                        dc, num, dn, y, y8, B, R, bias, affine, kadd, W.prep, nchs, shr, shr_r, cscale);
   }
   if (shr) {  // σ per row from the targets the Gram pass wrote into the prep
     float* sig = W.prep + (size_t)S * nchs * (s3_kn(dn, bias) == 16 ? s3_prep_floats<16>()
                                                                     : s3_prep_floats<32>());
     if (s3_kn(dn, bias) == 16)
-      hipLaunchKernelGGL(s3_sigma_kernel<16>, dim3(S_act), dim3(64), 0, gst, W.prep, nchs, B, R,
+      hipLaunchKernelGGL(s3_sigma_kernel<16>, dim3(S_act), dim3(64), 0, st, W.prep, nchs, B, R,
                          shr, shr_r, tbase, sig);
     else
-      hipLaunchKernelGGL(s3_sigma_kernel<32>, dim3(S_act), dim3(64), 0, gst, W.prep, nchs, B, R,
+      hipLaunchKernelGGL(s3_sigma_kernel<32>, dim3(S_act), dim3(64), 0, st, W.prep, nchs, B, R,
                          shr, shr_r, tbase, sig);
-  }
-  if (sd) {
-    hipEventRecord(sd->join, gst);
-    hipStreamWaitEvent(st, sd->join, 0);
   }
   return (int)hipGetLastError();
 }
@@ -2646,10 +2513,10 @@ static int s3_run_impl(int M, const float* const* w, float* const* dacc, double*
   const float* sig = shr ? W0.prep + (size_t)S * nchs * (kn == 16 ? s3_prep_floats<16>()
                                                                   : s3_prep_floats<32>())
                          : nullptr;
-  // latency form (mode 4): w0-margin workgroups + in-launch combiners beside the scans, the
-  // grid in waves of workgroups when it exceeds the GPU; throughput form (OMLDM_S3_FORM=2):
-  // one self-contained workgroup per spoke — helpers gather, the spoke combined by its own
-  // workgroup after its scan. Mode 3: helpers gather, in-launch combiners.
+  // mode 4: w0-margin workgroups + in-launch combiners beside the scans, the grid in waves of
+  // workgroups when it exceeds the GPU (pipelines beyond the GPU's CUs run in later waves: the
+  // pipeline-major block order needs no co-residency). Mode 3: helpers gather, in-launch
+  // combiners.
   static int ncu = 0;
   if (ncu == 0) {
     int dev = 0;
@@ -2660,35 +2527,15 @@ static int s3_run_impl(int M, const float* const* w, float* const* dacc, double*
   }
   int ncomb = g_s3_comb;
   bool rare = g_s3_mode == 4 && ncomb > 0;
-  bool tail = false;
-  int tailm = 0;
-  // auto = the latency form at every pipeline count (profiles/round5/mp_form*.json: 16
-  // pipelines 1.19 ms in three waves of workgroups vs 1.32 ms in the throughput form)
-  if (rare && g_s3_form == 2) {
-    rare = false;
-    tail = true;
-    ncomb = 0;
-  } else if (rare && g_s3_form == 3) {
-    tail = true;
-    ncomb = 0;
-  } else if (rare && g_s3_form == 4) {
-    tailm = 2;
-    ncomb = 0;
-  }
-  // spokes per combiner workgroup (OMLDM_S3_CNS, A/B): 1 — a combiner of 2 or 4 spokes falls
-  // behind its scans (16 pipelines: 1.20 / 1.27 / 1.67 ms, profiles/round5/mp_cns*.json)
-  int cns = g_s3_cns > 0 ? g_s3_cns : 1;
-  if (!rare || ncomb != 1) cns = 1;
   // in-scan combine: no combiner workgroups. Auto (past one workgroup per CU): no w0-margin
   // workgroups either — the helpers gather w0 and add the non-table occurrences (16
   // pipelines: one wave of 256 workgroups instead of three); forced: the w0-margin
   // workgroups while they fit, folding the non-table occurrences after their pass
-  const bool fits = (long long)M * s3_nper(S_act, rare, ncomb, cns) <= ncu;
-  const bool inscan = ncomb > 0 && g_s3_form < 2 && dim <= (1 << 22) &&
+  const bool fits = (long long)M * s3_nper(S_act, rare, ncomb) <= ncu;
+  const bool inscan = ncomb > 0 && dim <= (1 << 22) &&
                       (g_s3_inscan == 2 || (g_s3_inscan == 1 && !fits));
   if (inscan) {
     ncomb = 0;
-    cns = 1;
     rare = g_s3_inscan == 2 && g_s3_mode == 4 && (long long)M * 2 * S_act <= ncu;
   }
   S3Pipes pp{};
@@ -2696,7 +2543,7 @@ static int s3_run_impl(int M, const float* const* w, float* const* dacc, double*
   // the in-launch wait for the prep's ready word only while the scan grid leaves most CUs
   // to the prep's kernels (otherwise spinning LDS-heavy workgroups could hold the CUs the
   // prep needs until the bounded wait gives up): past that, the stream waits on the word
-  if (wflag && (long long)M * s3_nper(S_act, rare, ncomb, cns) > ncu / 2) {
+  if (wflag && (long long)M * s3_nper(S_act, rare, ncomb) > ncu / 2) {
     const hipError_t we = hipStreamWaitValue64(st, const_cast<unsigned long long*>(wflag),
                                                wepoch, hipStreamWaitValueGte, ~0ull);
     if (we != hipSuccess) return (int)we;
@@ -2705,7 +2552,6 @@ static int s3_run_impl(int M, const float* const* w, float* const* dacc, double*
   pp.wflag = wflag;
   pp.wepoch = wepoch;
   pp.ncomb = ncomb > 0 ? ncomb : 0;
-  pp.tail = tail ? 1 : tailm;
   for (int m = 0; m < M; ++m) {
     if (epoch[m] == 0u) return -2;
     const S3Ws Wm = s3_ws(ptrs + 8 * m);
@@ -2721,7 +2567,7 @@ static int s3_run_impl(int M, const float* const* w, float* const* dacc, double*
     pp.pipe[m] = S3Pipe{w[m], Wm.aglob, Wm.ws, Wm.wsd, rare ? Wm.gran + B : nullptr,
                         S3Comb{W0.lidcount, Wm.gran, epoch[m], S_act, dacc[m], inv_p[m],
                                static_cast<unsigned long long*>(arrive[m]), cum[m], sig,
-                               (flags & 2) ? 1 : 0, cns,
+                               (flags & 2) ? 1 : 0,
                                reinterpret_cast<const int*>(W0.meta + (size_t)dc * B),
                                gstride, inscan ? (rare ? 2 : 1) : 0},
                         p};
@@ -2733,7 +2579,7 @@ static int s3_run_impl(int M, const float* const* w, float* const* dacc, double*
   if (e) return e;
   for (int m = 0; m < M; ++m) {
     const S3Ws Wm = s3_ws(ptrs + 8 * m);
-    if (ncomb > 0 || tail || tailm || inscan) {  // the categorical slots were combined in the scan's launch
+    if (ncomb > 0 || inscan) {  // the categorical slots were combined in the scan's launch
       if (!arrive[m])
         hipLaunchKernelGGL(s3_tail_kernel, dim3(1), dim3(256), 0, st, Wm.ws, Wm.wsd, sig, S_act,
                            dn, dim, bias, inv_p[m], dacc[m], cum[m]);
@@ -2788,25 +2634,17 @@ OMLDM_API int omldm_scan3_part_bounds(int dim, int dn, int dc, long long span_in
   return 0;
 }
 
-OMLDM_API int omldm_scan3_hprio(int v) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_s3_hprio), &v, sizeof(v));
-}
-
-OMLDM_API int omldm_scan3_dense_order(int v) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_s3_dense_order), &v, sizeof(v));
-}
-
-OMLDM_API int omldm_scan3_debug(int v) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_s3_debug), &v, sizeof(v));
-}
-
 // MultiClassPA scan diagnostics: buf = u64 [S·8] (accumulated; null turns them off).
 OMLDM_API int omldm_scan3mc_debug(void* buf) {
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_s3mc_dbg), &buf, sizeof(buf));
 }
 
-OMLDM_API int omldm_scan3_stamps(void* buf) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_s3_stamps), &buf, sizeof(buf));
+// Scan phase cycles: buf = u64 [S·16] (accumulated; null turns them off). Slots 0, 1, 8, 9
+// are the scanner's, 2-7 those of helper wave `wave` of the workgroup (1 ..= NH; else -2).
+OMLDM_API int omldm_scan3_stamps(void* buf, int wave) {
+  if (wave < 1 || wave > s3::NH) return -2;
+  const int e = (int)hipMemcpyToSymbol(HIP_SYMBOL(g_s3_stamp_wave), &wave, sizeof(wave));
+  return e ? e : (int)hipMemcpyToSymbol(HIP_SYMBOL(g_s3_stamps), &buf, sizeof(buf));
 }
 
 // ------------------------------------------------------------------ MultiClassPA host API

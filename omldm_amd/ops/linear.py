@@ -440,8 +440,6 @@ class Scan3Prep:
 # the word in its workgroups (omldm_scan3_wait_next) instead of a cross-stream wait on the
 # prep's event: that barrier packet released the scan ~11 µs after the previous round's
 # apply (profiles/round5/devgap/: 0.311 → 0.292 ms per device-ingest round).
-# OMLDM_S3_READY=0: the event wait (A/B).
-_S3_READY_WAIT = os.environ.get("OMLDM_S3_READY", "1") != "0"
 _S3_READY: dict = {}
 
 
@@ -461,16 +459,18 @@ def _s3_ready_word(dev, slot):
 
 
 def _s3_wait_prep(sp, dev) -> None:
-    """Order the next v3 launch on the current stream after the prep ``sp``."""
-    if _S3_READY_WAIT and sp.ready is not None:
+    """Order the next v3 launch on the current stream after the prep ``sp`` (an inline prep,
+    or one made when the ready-word table is full, has no ready word: its event)."""
+    if sp.ready is not None:
         _s3_lib().omldm_scan3_wait_next(sp.ready[0], sp.ready[1])
     elif sp.event is not None:
         torch.cuda.current_stream(dev).wait_event(sp.event)
 
 
-# v3 table-scan kernel generation: 4 = the split spoke (a scanner and a table workgroup per
-# spoke, csrc/kernels/linear_scan3.hip: s4_scan_kernel), 3 = one workgroup per spoke with
-# in-launch combiners (the A/B reference). Fixed per process before the first prepare.
+# v3 round mode: 4 = a w0-margin workgroup beside each spoke's scan workgroup gathers the
+# round-start weights ahead of the scan (csrc/kernels/linear_scan3.hip: s3_rare), 3 = the
+# scan workgroup's helpers gather them themselves (the A/B reference). Fixed per process
+# before the first prepare.
 S3_MODE = int(os.environ.get("OMLDM_S3_MODE", "4"))
 _S3_MODE_SET = {"done": False}
 
@@ -479,9 +479,6 @@ def _s3_lib():
     h = native.hip()
     if not _S3_MODE_SET["done"]:
         h.omldm_scan3_set_mode(S3_MODE)
-        # A/B: the launch form (0 auto, 1 latency form always, 2 throughput form always)
-        h.omldm_scan3_set_form(int(os.environ.get("OMLDM_S3_FORM", "0")))
-        h.omldm_scan3_set_cns(int(os.environ.get("OMLDM_S3_CNS", "0")))
         # A/B: 0 = the combiner workgroups (the round-5 form) instead of the in-scan combine
         h.omldm_scan3_set_inscan(int(os.environ.get("OMLDM_S3_INSCAN", "1")))
         _S3_MODE_SET["done"] = True
@@ -677,10 +674,6 @@ def linear_scan3_prepare(batch: RawBatch, R: int, S: int, dim: int, bias: bool,
     32-bit category tokens, (``hashed``) int32 field-aware signed slots, or (``batch.span``
     > 0) the compact int16 field-aware slots of the engine's wire, row-major."""
     h = _s3_lib()
-    if "OMLDM_S3_GRAM_VALU" in os.environ:  # A/B: pass 3 on the VALU reference kernel
-        h.omldm_scan3_set_gram_valu(int(os.environ["OMLDM_S3_GRAM_VALU"]))
-    if "OMLDM_S3_PREP_SPLIT" in os.environ:  # A/B: 0 = flags and Grams on one stream
-        h.omldm_scan3_set_prep_split(int(os.environ["OMLDM_S3_PREP_SPLIT"]))
     dev = batch.y.device
     span = _s3_span(batch, dim)
     mode = _s3_mode(batch, hashed)
@@ -696,7 +689,7 @@ def linear_scan3_prepare(batch: RawBatch, R: int, S: int, dim: int, bias: bool,
     ev = torch.cuda.Event()  # pipelines on other streams that reuse the prep wait on it
     ev.record(st)
     ready = None
-    if stream is not None and _S3_READY_WAIT:
+    if stream is not None:
         ready = _s3_ready_word(dev, slot)
         if ready is not None:
             check(h.omldm_scan3_signal(ready[0], ready[1], st.cuda_stream), "omldm_scan3_signal")
@@ -712,8 +705,6 @@ def scan3_part_bounds(dim: int, dn: int, dc: int, part: int, parts: int,
           "omldm_scan3_part_bounds")
     return int(lh[0]), int(lh[1])
 
-
-_S3_TAIL_KERNEL = os.environ.get("OMLDM_S3_TAIL") == "kernel"
 
 # rounds run through the v3 scan in this process (tests: the engine's default path)
 SCAN3_ROUNDS = 0
@@ -745,8 +736,6 @@ def linear_scan3_round(w: torch.Tensor, batch: RawBatch, R: int, S: int, dacc: t
     global SCAN3_ROUNDS
     SCAN3_ROUNDS += 1
     h = _s3_lib()
-    if SCAN3_ROUNDS == 1 and "OMLDM_S3_COMB" in os.environ:  # A/B: 0 = combine after the scan
-        h.omldm_scan3_set_comb(int(os.environ["OMLDM_S3_COMB"]))
     parts = max(1, int(parts))
     span = _s3_span(batch, dim)
     # run-time buffers (c per row, spoke statistics, the table spill) per stream: pipelines
@@ -754,9 +743,8 @@ def linear_scan3_round(w: torch.Tensor, batch: RawBatch, R: int, S: int, dacc: t
     ptrs, gran = _s3_run_ptrs(sp, w.device, native.stream_of(w))
     epoch = _s3_next_epoch(gran)
     # the round's tail runs in the scan's launch (its last scan block) on an arrival word at
-    # the granule buffer's end (OMLDM_S3_TAIL=kernel: a separate kernel after the scan)
-    arrive = (None if _S3_TAIL_KERNEL else
-              gran[0].data_ptr() + (gran[0].numel() // 2 - 1) * 8)
+    # the granule buffer's end
+    arrive = gran[0].data_ptr() + (gran[0].numel() // 2 - 1) * 8
     for k in range(parts):
         flags = int(bool(dacc_zero)) | (2 if w.dtype == torch.bfloat16 else 0)
         rc = h.omldm_scan3_run(ptr(w), num.shape[1], batch.dc, ptr(y), int(y.dtype == torch.int8),
@@ -809,8 +797,7 @@ def linear_scan3_round_multi(ws: list, batch: RawBatch, R: int, S: int, daccs: l
         pm, gran = _s3_run_ptrs(sp, ws[m].device, stream, lane=m)
         ptrs += list(pm)
         epochs.append(_s3_next_epoch(gran))
-        arrives.append(None if _S3_TAIL_KERNEL else
-                       gran[0].data_ptr() + (gran[0].numel() // 2 - 1) * 8)
+        arrives.append(gran[0].data_ptr() + (gran[0].numel() // 2 - 1) * 8)
     cums = cums if cums is not None else [None] * M
     P = lambda ts: (ctypes.c_void_p * M)(*[ptr(t) for t in ts])  # noqa: E731
     F = lambda vs: (ctypes.c_float * M)(*[float(v) for v in vs])  # noqa: E731

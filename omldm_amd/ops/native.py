@@ -68,7 +68,6 @@ HIP_SIGS = [
     ("omldm_scan3_lds_cap", i32, []),
     ("omldm_scan3_set_cap", None, [i32]),
     ("omldm_scan3_set_gram_valu", None, [i32]),
-    ("omldm_scan3_set_gram_ablate", i32, [i32]),
     ("omldm_scan3_fits", i32, [i32, i32, i32, i32]),
     ("omldm_scan3_ws_words", i64, [i32, i32, i32, i32, i32, i32, i64, i32]),
     ("omldm_scan3_prepare", i32, [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32,
@@ -85,20 +84,16 @@ HIP_SIGS = [
     ("omldm_scan3mc_run", i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp,
                                 i32, f32, i32, vp, vp, vp, vp, vp, vp, vp]),
     ("omldm_scan3_set_comb", None, [i32]),
-    ("omldm_scan3_set_form", None, [i32]),
-    ("omldm_scan3_set_cns", None, [i32]),
     ("omldm_scan3_set_inscan", None, [i32]),
     ("omldm_scan3_wait_next", None, [vp, C.c_uint64]),
     ("omldm_scan3_signal", i32, [vp, C.c_uint64, vp]),
-    ("omldm_scan3_set_prep_split", None, [i32]),
     ("omldm_scan3_get_comb", i32, []),
     ("omldm_scan3_comb_err", i32, []),
     ("omldm_scan3_comb_err_drain", i32, [vp, vp]),
-    ("omldm_scan3_teardown", i32, []),
     ("omldm_scan3_set_mode", None, [i32]),
     ("omldm_scan3_get_mode", i32, []),
     ("omldm_scan3_part_bounds", i32, [i32, i32, i32, i64, i32, i32, vp]),
-    ("omldm_scan3_stamps", i32, [vp]),
+    ("omldm_scan3_stamps", i32, [vp, i32]),
     ("omldm_colstats_update", i32, [vp, i32, i32, C.c_double, vp, vp, vp, vp, i32, vp, i32, vp]),
     ("omldm_scale", i32, [vp, vp, i32, i32, i32, vp, vp, C.c_double, vp, vp, vp]),
     ("omldm_poly", i32, [vp, i32, i32, vp, i32, i32, vp, vp]),
@@ -275,21 +270,7 @@ def hip() -> _Lib:
                         f"{HIP_LIB_PATH} missing: the HIP kernels are required on GPU; "
                         "run python -m omldm_amd._build")
                 _hip = _Lib(HIP_LIB_PATH, HIP_SIGS)
-                import atexit
-
-                atexit.register(_hip_teardown)
     return _hip
-
-
-def _hip_teardown() -> None:
-    """Destroy the streams / events the kernel library created on demand while the HIP
-    runtime is still up (Python's atexit runs before the shared libraries' finalizers)."""
-    lib = _hip
-    if lib is not None and getattr(lib, "omldm_scan3_teardown", None) is not None:
-        try:
-            lib.omldm_scan3_teardown()
-        except Exception:  # noqa: BLE001 - best effort at exit
-            pass
 
 
 def check(rc: int, what: str) -> None:

@@ -2,7 +2,6 @@
 """v3 table scan at the headline geometry (16 spokes × 8192 rows, 2^20 slots): device time
 of the prepare (passes 1-3) and of the run (scan + combine) per round, and the scan
 kernel's per-phase cycles per chunk (linear_scan3.hip stamps). Diagnostics only (GPU)."""
-import ctypes
 import json
 import os
 import sys
@@ -43,74 +42,32 @@ for _ in range(n):
     tp += ev[0].elapsed_time(ev[1])
     tr += ev[1].elapsed_time(ev[2])
     b.prep = None
-lib = native.hip().cdll
-lib.omldm_scan3_stamps.argtypes = [ctypes.c_void_p]
-st = torch.zeros((S, 16), dtype=torch.int64, device=dev)
-lib.omldm_scan3_stamps(st.data_ptr())
-L.linear_seq_round(w, b, R, S, dacc, rule, 1.0 / S, cum=cum)
-torch.cuda.synchronize()
-lib.omldm_scan3_stamps(None)
-m = st.double().mean(0)
-nch = (R + 63) // 64 + 2
+lib = native.hip()
 names = ["scan_tail", "scan_bar", "h_top_wait", "h_issue", "h_margins", "h_lds_prefetch",
          "h_scatter", "h_bar", "scan_head", "scan_chain"]
+nch = (R + 63) // 64 + 2
+st = torch.zeros((S, 16), dtype=torch.int64, device=dev)
+
+
+def stamped_round(wave):
+    """Mean cycles per phase over the spokes of one round, helper wave `wave` stamped."""
+    st.zero_()
+    lib.omldm_scan3_stamps(st.data_ptr(), wave)
+    L.linear_seq_round(w, b, R, S, dacc, rule, 1.0 / S, cum=cum)
+    torch.cuda.synchronize()
+    lib.omldm_scan3_stamps(None, 1)
+    return st.double().mean(0)
+
+
+m = stamped_round(1)
 print(json.dumps({"prepare_ms": round(tp / n, 4), "run_ms": round(tr / n, 4),
                   "Mex_s": round(S * R / ((tp + tr) / n) / 1e3, 1),
                   "stamps_cycles_per_chunk": {names[k]: round(float(m[k]) / nch, 1)
                                               for k in range(10)}}), flush=True)
 
-# latency experiment: every gather reads w[0] (wrong model, timing only)
-lib.omldm_scan3_debug.argtypes = [ctypes.c_int]
-lib.omldm_scan3_debug(1)
-st.zero_()
-lib.omldm_scan3_stamps(st.data_ptr())
-L.linear_seq_round(w, b, R, S, dacc, rule, 1.0 / S, cum=cum)
-torch.cuda.synchronize()
-lib.omldm_scan3_stamps(None)
-lib.omldm_scan3_debug(0)
-m = st.double().mean(0)
-print(json.dumps({"gathers_hit_w0": {names[k]: round(float(m[k]) / nch, 1)
-                                     for k in range(10)}}), flush=True)
-
-# per helper wave (g_s3_debug = 16 + wave selects the stamped helper): which helper sets
-# the chunk period (waves 4 and 8 share the scanner's SIMD)
+# per helper wave: which helper sets the chunk period (waves 4 and 8 share the scanner's SIMD)
 per = {}
 for wv in range(1, 12):
-    lib.omldm_scan3_debug(16 + wv)
-    st.zero_()
-    lib.omldm_scan3_stamps(st.data_ptr())
-    L.linear_seq_round(w, b, R, S, dacc, rule, 1.0 / S, cum=cum)
-    torch.cuda.synchronize()
-    lib.omldm_scan3_stamps(None)
-    m = st.double().mean(0)
+    m = stamped_round(wv)
     per[wv] = {names[k]: round(float(m[k]) / nch) for k in range(2, 8)}
-lib.omldm_scan3_debug(0)
 print(json.dumps({"helper_waves": per}), flush=True)
-if os.environ.get("PROBE_HPRIO"):
-    lib.omldm_scan3_hprio.argtypes = [ctypes.c_int]
-    for v in (0, 1, 0, 1):
-        lib.omldm_scan3_hprio(v)
-        torch.cuda.synchronize()
-        ev[0].record()
-        for _ in range(n):
-            L.linear_seq_round(w, b, R, S, dacc, rule, 1.0 / S, cum=cum)
-            L.linear_apply(w, None, dacc)
-        ev[1].record()
-        torch.cuda.synchronize()
-        print(json.dumps({"hprio": v, "run_ms": round(ev[0].elapsed_time(ev[1]) / n, 4)}),
-              flush=True)
-    lib.omldm_scan3_hprio(0)
-if os.environ.get("PROBE_DENSE_ORDERS"):
-    lib.omldm_scan3_dense_order.argtypes = [ctypes.c_int]
-    for order in (0, 1):
-        lib.omldm_scan3_dense_order(order)
-        torch.cuda.synchronize()
-        ev[0].record()
-        for _ in range(n):
-            L.linear_seq_round(w, b, R, S, dacc, rule, 1.0 / S, cum=cum)
-            L.linear_apply(w, None, dacc)
-        ev[1].record()
-        torch.cuda.synchronize()
-        print(json.dumps({"dense_order": order, "run_ms": round(ev[0].elapsed_time(ev[1]) / n, 4)}),
-              flush=True)
-    lib.omldm_scan3_dense_order(0)
