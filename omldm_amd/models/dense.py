@@ -258,7 +258,11 @@ class MultiClassPA(Learner):
     round (csrc/kernels/multiclass_dense.hip: the K × (dn + bias) prototypes in LDS, exact
     sequential spokes, K ≤ 256, fp32 prototypes; ops/dense.py ``multiclass_dense_fits``);
     the field-aware wire with K ≤ 16 the v3 table scan (csrc/kernels/linear_scan3.hip:
-    s3mc_scan_kernel); everything else the spoke tables (csrc/kernels/multiclass_spoke.hip)."""
+    s3mc_scan_kernel); a batch with categorical columns and more than 16 classes or more than
+    64 features per row the wide round (csrc/kernels/multiclass_wide.hip: lane = class, the
+    spoke's delta in an HBM table, K ≤ 256, ≤ 256 features, fp32 prototypes; ops/dense.py
+    ``multiclass_wide_fits``); everything else the spoke tables
+    (csrc/kernels/multiclass_spoke.hip)."""
 
     NAME = "MultiClassPA"
     TASK = "classification"
@@ -344,6 +348,15 @@ class MultiClassPA(Learner):
             # exact sequential spokes on the v3 table scan (K ≤ 16, field-aware wire)
             D.multiclass_scan3_round(self.Wt, batch, R, S, self.K, self.variant, self.C,
                                      self.bias, self.dacc, self.st)
+        elif (self.W.is_cuda and D.MC_WIDE and self.Wt is not None
+              and self.Wt.dtype == torch.float32 and batch.dc > 0
+              and (self.K > 16 or batch.dn + batch.dc + int(self.bias) > 64)
+              and D.multiclass_wide_fits(batch.dn, batch.dc, self.bias, self.K, R, S,
+                                         batch.cat_span, self.dim)):
+            # past the scan's and the spoke tables' box (they refuse it): lane = class, the
+            # spoke's delta in an HBM table (K ≤ 256, ≤ 256 features per row)
+            D.multiclass_wide_round(self.W, self.Wt, batch, R, S, self.K, self.variant, self.C,
+                                    self.bias, self.dacc, self.st)
         else:  # the spoke-table round (LDS delta tables spilling to HBM)
             D.multiclass_round(self.W, batch, R, S, self.K, self.variant, self.C, self.bias,
                                self.dacc, self.st, log2cap=hp_int(self.hyper, "tableLog2", 0),

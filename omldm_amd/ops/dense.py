@@ -231,6 +231,115 @@ def multiclass_dense_round(W: torch.Tensor, batch: HashedBatch, R: int, S: int, 
         "omldm_multiclass_dense_round")
 
 
+# ------------------------------------------- wide MultiClassPA round (hashed batches, K ≤ 256)
+# Batches with categorical columns past the scan's and the spoke tables' box (K > 16 or more
+# than 64 features per row): one workgroup per spoke, lane = class, the spoke's private delta
+# in an HBM table of class_pad(K) floats per hashed key (csrc/kernels/multiclass_wide.hip).
+# OMLDM_MC_WIDE=0 restores the routing without it.
+MC_WIDE = os.environ.get("OMLDM_MC_WIDE", "1") != "0"
+MC_WIDE_MAX_F = 256       # kMcwMaxF: features per row (dn + dc + bias)
+MC_WIDE_MAX_K = 256       # kMcwMaxK
+MC_WIDE_MAX_LOG2 = 24     # kMcwMaxLog2: table entries per spoke
+# HBM the tables of one round may take (OMLDM_MC_WIDE_BUDGET_MB, default 16 GiB ≈ 5 % of the
+# card: K = 256 at 16 spokes × 8192 rows with 26 categorical fields takes ≈ 8.6 GB)
+MC_WIDE_BUDGET = int(os.environ.get("OMLDM_MC_WIDE_BUDGET_MB", "16384")) << 20
+# rounds run through the wide kernel in this process (tests)
+MC_WIDE_ROUNDS = 0
+# (device, stream) → ((S, log2, kp), table): the most recent table only — these are gigabytes
+_MC_WIDE_WS: dict = {}
+
+
+def multiclass_wide_table_log2(R: int, dn: int, dc: int, bias: bool, cspan: int, dim: int) -> int:
+    """log2 of the wide round's table entries per spoke: the smallest power of two ≥ 2 × the
+    spoke's worst-case distinct keys, dn + bias + min(R·dc, hashed key range); the range is
+    dc·cspan on the compact wire and dim − dn − 1 on the wide one (mcw_table_log2 draws the
+    same line)."""
+    rng = int(dc) * int(cspan) if cspan > 0 else int(dim) - int(dn) - 1
+    distinct = int(dn) + int(bool(bias)) + min(int(R) * int(dc), max(0, rng))
+    return max(0, 2 * distinct - 1).bit_length()
+
+
+def multiclass_wide_fits(batch_dn: int, batch_dc: int, bias: bool, nclass: int, R: int, S: int,
+                         cspan: int, dim: int) -> bool:
+    """The wide MultiClassPA round's shape: 2 ≤ K ≤ 256 classes, 1 ≤ F = dn + dc + bias ≤ 256
+    features per row, and S tables of 2^log2 entries of (2 + class_pad(K)) words (plus the S
+    counters) within the round's HBM budget. omldm_multiclass_wide_fits draws the same line
+    for one table."""
+    dn, dc, K = int(batch_dn), int(batch_dc), int(nclass)
+    F = dn + dc + int(bool(bias))
+    if not (dn >= 0 and dc >= 0 and 1 <= F <= MC_WIDE_MAX_F and 2 <= K <= MC_WIDE_MAX_K
+            and R >= 1 and S >= 1 and dim >= 1 and cspan >= 0):
+        return False
+    lg = multiclass_wide_table_log2(R, dn, dc, bias, cspan, dim)
+    if not 1 <= lg <= MC_WIDE_MAX_LOG2:
+        return False
+    words = int(S) * (1 << lg) * (2 + class_pad(K)) + int(S)
+    return words * 4 <= MC_WIDE_BUDGET
+
+
+def multiclass_wide_workspace(device, S: int, log2gcap: int, kp: int,
+                              fresh: bool = False) -> torch.Tensor:
+    """The S spokes' delta tables for the current stream (spoke_table.h: Spill; keys −1, every
+    other word 0 when allocated; every round restores what it used). One buffer per device
+    and stream: another geometry replaces it. ``fresh``: a new buffer whatever is cached."""
+    dev = torch.device(device)
+    k = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
+    geom = (int(S), int(log2gcap), int(kp))
+    hit = _MC_WIDE_WS.get(k)
+    if hit is not None and hit[0] == geom and not fresh:
+        return hit[1]
+    _MC_WIDE_WS.pop(k, None)  # free the old table before the new one is allocated
+    hit = None
+    n = int(S) << int(log2gcap)
+    t = torch.zeros(n * (2 + int(kp)) + int(S), dtype=torch.int32, device=dev)
+    t[:n].fill_(-1)
+    _MC_WIDE_WS[k] = (geom, t)
+    return t
+
+
+def multiclass_wide_round(W: torch.Tensor, Wt: torch.Tensor | None, batch: HashedBatch, R: int,
+                          S: int, nclass: int, variant: int, C: float, bias: bool,
+                          dacc: torch.Tensor, stats: torch.Tensor) -> None:
+    """S exact sequential MultiClassPA spokes of R rows on a hashed batch (GPU;
+    ``multiclass_wide_fits``), with the contract of ``multiclass_round``: dacc[K, dim] +=
+    Σ_s Δ_s, stats[0..3] += (loss, rows, mistakes, spokes with rows), stats[5] stays 0. ``Wt``:
+    the fp32 key-major shadow [dim, class_pad(K)] (made from ``W`` when None). The compact or
+    wide categorical wire, bf16 or fp32 numerical features and fp32 or int8 labels are read as
+    they are. The spokes fold in spoke order without float atomics: the same inputs give the
+    same bits."""
+    from omldm_amd.ops.linear import _workspace
+
+    if S <= 0 or batch.B == 0:
+        return
+    K, dim = W.shape
+    kp = class_pad(nclass)
+    num, cat, y = batch.num, batch.cat, batch.y
+    dn, dc, cspan = int(batch.dn), int(batch.dc), int(batch.cat_span)
+    assert K == nclass and multiclass_wide_fits(dn, dc, bias, nclass, R, S, cspan, dim)
+    assert W.is_cuda and dacc.is_cuda and dacc.dtype == torch.float32 and dacc.is_contiguous()
+    assert dacc.shape == W.shape
+    assert stats.is_cuda and stats.dtype == torch.float32 and stats.numel() >= 6
+    if Wt is None:
+        Wt = proto_shadow(W)
+    assert Wt.dtype == torch.float32 and Wt.shape == (dim, kp) and Wt.is_contiguous()
+    assert num.dtype in (torch.float32, torch.bfloat16) and y.dtype in (torch.float32, torch.int8)
+    assert cat.dtype == (torch.int16 if cspan > 0 else torch.int32)
+    assert all(t.is_contiguous() for t in (num, cat, y))
+    assert all(t.is_cuda or t.is_pinned() for t in (num, cat, y) if t.numel())
+    assert variant in (0, 1, 2) and C > 0
+    global MC_WIDE_ROUNDS
+    MC_WIDE_ROUNDS += 1
+    lg = multiclass_wide_table_log2(R, dn, dc, bias, cspan, dim)
+    table = multiclass_wide_workspace(W.device, S, lg, kp)
+    ws = _workspace(W.device, S * 8, key="mc_wide_ws")
+    dp = native.dptr
+    check(native.hip().omldm_multiclass_wide_round(
+        ptr(Wt), 0, dp(num) if dn else None, int(num.dtype == torch.bfloat16), dn,
+        dp(cat) if dc else None, dc, cspan, dp(y), int(y.dtype == torch.int8), batch.B, R, S, dim,
+        nclass, int(variant), float(C), int(bool(bias)), ptr(dacc), ptr(stats), ptr(ws),
+        ptr(table), lg, native.stream_of(W)), "omldm_multiclass_wide_round")
+
+
 def kmeans_seq(x: torch.Tensor, y: torch.Tensor | None, cent: torch.Tensor, n: torch.Tensor,
                cum: torch.Tensor | None) -> None:
     """Exact sequential (MacQueen) k-means over the rows of x, in order (GPU:

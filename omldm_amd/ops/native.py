@@ -111,6 +111,9 @@ HIP_SIGS = [
     ("omldm_multiclass_dense_ws_words", i64, [i32, i32, i32]),
     ("omldm_multiclass_dense_round", i32, [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32,
                                            f32, i32, vp, vp, vp, vp]),
+    ("omldm_multiclass_wide_fits", i32, [i32, i32, i32, i32, i32, i32, i32, i32]),
+    ("omldm_multiclass_wide_round", i32, [vp, i32, vp, i32, i32, vp, i32, i32, vp, i32, i32, i32,
+                                          i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, i32, vp]),
     ("omldm_multiclass_apply", i32, [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp]),
     ("omldm_mlp_lds_bytes", i64, [i32, vp]),
     ("omldm_mlp_round", i32, [vp, vp, vp, i64, i32, i32, i32, vp, i32, i32, f32, vp, vp, vp, vp,
