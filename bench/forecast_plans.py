@@ -16,6 +16,14 @@ Predictions produced, ``ForecastServer.latency_percentiles``) — the baseline f
 compare against — and, for the Python lane, ``family_us`` per learner.
 
     python bench/forecast_plans.py [--records 1000] [--out profiles/round7/forecast_plans.json]
+
+``--nonlinear``: the two learners ``plans`` leaves to one-row predicts — an NN with the
+default hidden layers [32, 32] and an HT with the defaults, trained on the same block — are
+added, and ``--forecastServer plans`` (the baseline here: those two are one-row predicts, the
+code path of the commit before ``plans-all``) is compared with ``--forecastServer plans-all``
+(both on the wave): the six pipelines in one job, and the NN and the HT each alone, whose
+``publish_us`` is the cost of the two new ``serving_write``. Default output:
+profiles/round7/forecast_plans_all.json.
 """
 from __future__ import annotations
 
@@ -41,6 +49,10 @@ PIPELINES = {
     "ORR+PolynomialFeatures(2)": ("ORR", {}, ["PolynomialFeatures"]),
     "MultiClassPA(K=4)": ("MultiClassPA", {"nClasses": 4}, []),
     "K-means(k=16)": ("K-means", {"k": 16}, []),
+}
+NONLINEAR = {
+    "NN[32,32]": ("NN", {}, []),
+    "HT": ("HT", {}, []),
 }
 
 
@@ -88,7 +100,7 @@ def measure(mode: str, names: list[str], n: int, block: bytes, recs: list[bytes]
                   torch.device("cuda", torch.cuda.current_device()))
         try:
             for i, name in enumerate(names):
-                learner, hyper, pre = PIPELINES[name]
+                learner, hyper, pre = {**PIPELINES, **NONLINEAR}[name]
                 br.produce("requests", json.dumps({
                     "id": i + 1, "request": "Create",
                     "learner": {"name": learner, "hyperParameters": hyper},
@@ -152,6 +164,10 @@ def measure(mode: str, names: list[str], n: int, block: bytes, recs: list[bytes]
                    "lane_own_us": fs.latency_percentiles(),
                    "publish_us": {"host_enqueue_p50": _pct(pub_host)["p50"],
                                   "device_p50": _pct(pub_dev)["p50"]}}
+            trees = {names[pid - 1]: int(pipe.learner.nnodes.item())
+                     for pid, pipe in sorted(job.pipes.items()) if pipe.learner.NAME == "HT"}
+            if trees:
+                out["tree_nodes"] = trees
             if fs.native:
                 out["native_stage_us"] = fs.native_stats()["stage_us"]
             else:
@@ -164,9 +180,13 @@ def measure(mode: str, names: list[str], n: int, block: bytes, recs: list[bytes]
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=1000)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "round7",
-                                                  "forecast_plans.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--nonlinear", action="store_true",
+                    help="add an NN and an HT; compare plans with plans-all")
     a = ap.parse_args(argv)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "round7", "forecast_plans_all.json"
+                             if a.nonlinear else "forecast_plans.json")
     from omldm_amd.io.synthetic import synth_json_records
 
     sp = FeatureSpace(NUM, 0, CAT, DIM)
@@ -179,12 +199,20 @@ def main(argv=None) -> int:
            "unit": "us per record, appended to the forecasting topic -> Predictions appended",
            "baseline_flag": "true", "plans_flag": "plans", "job": {}, "alone": {}}
     names = list(PIPELINES)
-    for mode, key in (("true", "baseline"), ("plans", "plans")):
+    modes = (("true", "baseline"), ("plans", "plans"))
+    alone = names
+    if a.nonlinear:
+        res["bench"] = "forecast_plans_all"
+        res["baseline_flag"], res["plans_flag"] = "plans", "plans-all"
+        names = names + list(NONLINEAR)
+        modes = (("plans", "baseline"), ("plans-all", "plans"))
+        alone = list(NONLINEAR)
+    for mode, key in modes:
         res["job"][key] = measure(mode, names, a.records, block, recs)
         print(json.dumps({"job": key, **res["job"][key]}), flush=True)
-    for name in names:
+    for name in alone:
         res["alone"][name] = {}
-        for mode, key in (("true", "baseline"), ("plans", "plans")):
+        for mode, key in modes:
             r = measure(mode, [name], a.records, block, recs)
             res["alone"][name][key] = r
             print(json.dumps({"alone": name, "mode": key, **r}), flush=True)

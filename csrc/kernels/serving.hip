@@ -29,7 +29,8 @@
 // * serve_plan_kernel: a plan (serve_plan.h), one entry per pipeline — StandardScaler /
 //   MinMaxScaler (a per-lane (x − shift) / div) and PolynomialFeatures(2) (a product of two
 //   lanes) in front of a hashed-linear or dense ridge row, the K rows of a MultiClassPA
-//   (argmax on the device) or the k centroids of a K-means (argmin on the device), all
+//   (argmax on the device), the k centroids of a K-means (argmin on the device), a small MLP
+//   (≤ 4 layers of ≤ 64 units) or a Hoeffding tree (≤ 1024 nodes, ≤ 32 classes), all
 //   evaluated by the one wave from the request line it already holds
 //   (omldm_serve_plan_start; CPU mirror: csrc/host/serve_plan_cpu.cpp).
 #include "common.h"
@@ -206,6 +207,148 @@ __device__ __forceinline__ int plan_word(const int* e, int i) {
   return __builtin_amdgcn_readfirstlane(e[i]);
 }
 
+// ---- kPlanMlp / kPlanTree (the NL instantiation of serve_plan_kernel only) ------------------
+__device__ __forceinline__ float plan_act(float v, int act) {
+  switch (act) {
+    case 0: return fmaxf(v, 0.f);
+    case 1: return tanhf(v);
+    case 2: return 1.f / (1.f + expf(-v));
+    default: return v;
+  }
+}
+
+// A multi-layer perceptron of at most 4 layers of at most 64 units. Lane j owns unit j of the
+// current layer: acc = b[j], then one fma per input i in index order (a single accumulator —
+// the arithmetic of the CPU mirror), h_i broadcast from lane i with a wave-uniform readlane.
+// Wt is input-major, so for a fixed i the lanes read consecutive floats; a layer's loads (its
+// bias and its ≤ 64 rows) are all issued before its fma chain: one round trip per layer.
+// The next layer's rows are not prefetched during the chain: its extents depend on nothing
+// but the plan, yet holding two layers' rows would double the live registers for a chain of
+// ≤ 64 fmas (≈ 0.1 µs) — the loads of a ≤ 17 KB layer are L2 hits after the first request.
+__device__ __forceinline__ float plan_mlp(const float* __restrict__ A, const int* e, int off,
+                                          int width, float v, int D, int lane) {
+  const int* a = e + kPlAux;
+  const int L = min(plan_word(a, 0), kPlanMlpMaxLayers);
+  const int act = plan_word(a, 1), task = plan_word(a, 2);
+  int win = min(plan_word(a, 3), kPlanLanes);
+  float h = lane < min(D, win) ? v : 0.f;
+  long long o = off;
+  const long long end = (long long)off + width;
+  float acc = 0.f;
+  int wout = 1;
+  for (int l = 0; l < L; ++l) {
+    wout = min(max(plan_word(a, 4 + l), 1), kPlanLanes);
+    if (o < 0 || o + (long long)win * wout + wout > end) return 0.f;  // outside the region
+    const float* __restrict__ W = A + o;
+    const bool on = lane < wout;
+    acc = on ? W[win * wout + lane] : 0.f;
+    float wv[kPlanLanes];
+#pragma unroll
+    for (int i = 0; i < kPlanLanes; ++i) wv[i] = (on && i < win) ? W[i * wout + lane] : 0.f;
+#pragma unroll
+    for (int i = 0; i < kPlanLanes; ++i) {
+      if (i < win) acc = fmaf(wv[i], readlane_f(h, i), acc);  // wave-uniform
+    }
+    if (l + 1 < L) acc = plan_act(acc, act);
+    h = on ? acc : 0.f;
+    o += (long long)win * wout + wout;
+    win = wout;
+  }
+  const float s0 = readlane_f(h, 0);
+  if (task == 0) return s0;
+  if (task == 1) return s0 >= 0.f ? 1.f : -1.f;
+  float bv = lane < wout ? h : -INFINITY;  // argmax over the outputs, the lowest index on a tie
+  int bi = lane < wout ? lane : 0x7fffffff;
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) {
+    const float ov = __shfl_xor(bv, s, 64);
+    const int oi = __shfl_xor(bi, s, 64);
+    if (ov > bv || (ov == bv && oi < bi)) {
+      bv = ov;
+      bi = oi;
+    }
+  }
+  bi = __builtin_amdgcn_readfirstlane(bi);
+  return (unsigned)bi < (unsigned)wout ? (float)bi : 0.f;
+}
+
+// A Hoeffding tree (the head of HT.state: feat, thr, left, right, cc). A node-by-node walk of
+// the arena is two dependent global loads per level; instead every lane loads its nodes
+// lane, lane + 64, … of the four arrays in one round trip, decides each node's successor for
+// this point (x[f] ≤ thr ? left : right; "stop" on a leaf, on a feature outside [0, D) — or
+// [0, D + D(D+1)/2) behind a lazy poly2 stage — or a child outside [0, N)) and writes it to LDS; the chain from node 0 is then followed through
+// LDS for at most depth + 1 steps (ht_route's bound; depth is clamped to the node limit — a
+// path in a tree of ≤ 1024 nodes is shorter). The reached node's class counts are read by C
+// lanes; argmax, the lowest class on a tie (ht_predict_kernel).
+__device__ __forceinline__ float plan_tree(const float* __restrict__ A, const int* e, int off,
+                                           int width, float v, int D, bool lazy, int lane,
+                                           short* s_next) {
+  const int* a = e + kPlAux;
+  const int N = min(max(plan_word(a, 0), 1), kPlanTreeMaxNodes);
+  const int C = min(max(plan_word(a, 1), 1), kPlanTreeMaxClasses);
+  const int steps = min(max(plan_word(a, 2), 0), kPlanTreeMaxNodes) + 1;
+  if (off < 0 || (long long)N * (4 + C) > width) return 0.f;  // outside the region
+  const float* __restrict__ T = A + off;
+  constexpr int kPer = kPlanTreeMaxNodes / kPlanLanes;
+  float nf[kPer], nt[kPer], nl[kPer], nr[kPer];
+#pragma unroll
+  for (int u = 0; u < kPer; ++u) {
+    const int n = u * kPlanLanes + lane;
+    const bool on = n < N;
+    nf[u] = on ? T[n] : -1.f;
+    nt[u] = on ? T[N + n] : 0.f;
+    nl[u] = on ? T[2 * N + n] : -1.f;
+    nr[u] = on ? T[3 * N + n] : -1.f;
+  }
+  const float xv = lane < D ? v : 0.f;
+  // behind a lazy poly2 stage (wave-uniform) the features are the D lanes, then the
+  // D(D+1)/2 pair products: feature D + p = lane a · lane b of pair p (poly2_pair)
+  const int DF = lazy ? D + D * (D + 1) / 2 : D;
+#pragma unroll
+  for (int u = 0; u < kPer; ++u) {
+    if (u * kPlanLanes < N) {  // wave-uniform
+      const int n = u * kPlanLanes + lane;
+      const bool inner = nf[u] >= 0.f && nf[u] < (float)DF;
+      const int f = inner ? (int)nf[u] : 0;
+      int fa = f, fb = -1;
+      if (f >= D) poly2_pair(f - D, D, &fa, &fb);
+      float x = __shfl(xv, fa & 63, 64);
+      if (lazy) {  // wave-uniform: the shuffle runs in every lane
+        const float xb = __shfl(xv, fb & 63, 64);
+        if (fb >= 0) x *= xb;
+      }
+      const float ch = x <= nt[u] ? nl[u] : nr[u];
+      const bool go = inner && ch >= 0.f && ch < (float)N;
+      if (n < N) s_next[n] = go ? (short)(int)ch : (short)-1;
+    }
+  }
+  __syncthreads();
+  int node = 0;
+  for (int it = 0; it < steps; ++it) {
+    const int nx = s_next[node];  // the same address in every lane: one LDS broadcast
+    if (nx < 0) break;
+    node = nx;
+  }
+  node = __builtin_amdgcn_readfirstlane(node);
+  __syncthreads();  // the next tree entry rewrites s_next
+  float bv = lane < C ? T[(size_t)4 * N + (size_t)node * C + lane] : -INFINITY;
+  int bi = lane < C ? lane : 0x7fffffff;
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) {
+    const float ov = __shfl_xor(bv, s, 64);
+    const int oi = __shfl_xor(bi, s, 64);
+    if (ov > bv || (ov == bv && oi < bi)) {
+      bv = ov;
+      bi = oi;
+    }
+  }
+  bi = __builtin_amdgcn_readfirstlane(bi);
+  return (unsigned)bi < (unsigned)C ? (float)bi : 0.f;
+}
+
+// NL: the instantiation that also knows kPlanMlp and kPlanTree entries (and holds the tree's
+// successor table in LDS); a plan without them runs the other one.
+template <bool NL>
 __global__ __launch_bounds__(64) void serve_plan_kernel(const int* __restrict__ plan, int M,
                                                         const float* __restrict__ a0,
                                                         const float* __restrict__ a1, int dn, int dc,
@@ -286,10 +429,13 @@ __global__ __launch_bounds__(64) void serve_plan_kernel(const int* __restrict__ 
       // stages, on the dense lanes only
       float v = x0;
       int D = dn;
+      [[maybe_unused]] bool lazy = false;
       for (int s = 0; s < ns; ++s) {
         const int* st = e + kPlStage0 + 4 * s;
         const int type = plan_word(st, 0), pa = plan_word(st, 1), pb = plan_word(st, 2);
-        if (type == kPlanAffine) {
+        if (NL && type == kPlanPoly2Lazy) {
+          lazy = true;  // (a tree's last stage: the products are taken per node, plan_tree)
+        } else if (type == kPlanAffine) {
           if (lane < D) v = (v - A[pa + lane]) / A[pb + lane];
         } else {  // kPlanPoly2: lanes [D, D + D(D+1)/2) take the pair products
           const int np = D * (D + 1) / 2;
@@ -302,7 +448,19 @@ __global__ __launch_bounds__(64) void serve_plan_kernel(const int* __restrict__ 
         }
       }
       float r;
-      if (kind == kPlanKmeans) {
+      bool nonlinear = false;
+      if constexpr (NL) {
+        __shared__ short s_next[kPlanTreeMaxNodes];
+        if (kind == kPlanMlp) {
+          r = plan_mlp(A, e, off, width, v, D, lane);
+          nonlinear = true;
+        } else if (kind == kPlanTree) {
+          r = plan_tree(A, e, off, width, v, D, lazy, lane, s_next);
+          nonlinear = true;
+        }
+      }
+      if (nonlinear) {
+      } else if (kind == kPlanKmeans) {
         // lane j owns centroid c0 + j; x_f is broadcast, the distance accumulates in column
         // order with one fma per column (the arithmetic of kmeans_assign_kernel)
         const int dd_w = min(D, width);
@@ -470,9 +628,16 @@ OMLDM_API int omldm_serve_plan_start(const int* plan, int n_models, const float*
   __atomic_store_n(&hmb->exit_reason, 0u, __ATOMIC_SEQ_CST);
   __atomic_store_n(&hmb->alive, 0u, __ATOMIC_SEQ_CST);
   const unsigned long long ticks = (unsigned long long)lifetime_us * 100ull;  // 100 MHz
-  hipLaunchKernelGGL(serve_plan_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
-                     (const int*)dplan, n_models, arena0, arena1, dn, dc, dim, cspan,
-                     (Mailbox*)dmb, ticks);
+  // a plan of linear / multi-class / k-means entries runs the instantiation without the MLP
+  // and tree code (and without the tree's LDS table)
+  if (plan_has_nonlinear(plan, n_models))
+    hipLaunchKernelGGL(serve_plan_kernel<true>, dim3(1), dim3(64), 0, (hipStream_t)stream,
+                       (const int*)dplan, n_models, arena0, arena1, dn, dc, dim, cspan,
+                       (Mailbox*)dmb, ticks);
+  else
+    hipLaunchKernelGGL(serve_plan_kernel<false>, dim3(1), dim3(64), 0, (hipStream_t)stream,
+                       (const int*)dplan, n_models, arena0, arena1, dn, dc, dim, cspan,
+                       (Mailbox*)dmb, ticks);
   return (int)hipGetLastError();
 }
 

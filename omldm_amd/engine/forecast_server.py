@@ -32,6 +32,18 @@ past the wave's limits (64 lanes, 4 stages, degree-2 maps) keep the one-row pred
 whose pipelines are all plan-served runs the native lane, which needs no change: it sees
 ``M`` outputs, none of them to be thresholded.
 
+``--forecastServer plans-all`` (opt-in as well; ``plans`` is unchanged) is ``plans`` with
+the two remaining learners on the wave (``build_plan(..., nonlinear=True)``): an NN of at
+most 4 layers of at most 64 units with fp32 matmuls (its forward pass, one unit per lane,
+the weights published input-major) and a Hoeffding tree of at most 1024 nodes and 32
+classes (the head of its state vector as it lies; the wave decides every node's successor
+at once and follows the chain through LDS; directly behind PolynomialFeatures(2) it is
+served even where the map is wider than the wave's lanes — a node's product is taken from
+two lanes). Wider networks, bf16-matmul networks and larger
+trees keep the one-row predicts. An NN's activation is a word of its plan entry, so in this
+mode an ``Update`` request reconfigures the server like a Create or a Delete
+(engine/job.py). One NN or HT pipeline no longer keeps a job off the native lane.
+
 Consistency (the reference serialises a spoke's predict and fit in one operator,
 FlinkSpoke.scala:97-105, so a prediction sees a model between two fits):
 
@@ -95,9 +107,11 @@ class ForecastServer:
     SPIN_S = 2e-3
     WARM_S = 50e-3
 
-    def __init__(self, job, lifetime_us: int = 2_000_000, plans: bool = False):
+    def __init__(self, job, lifetime_us: int = 2_000_000, plans: bool = False,
+                 nonlinear: bool = False):
         self.job = job
         self.plans = bool(plans)      # --forecastServer plans: the plan-driven wave
+        self.nonlinear = bool(nonlinear)  # plans-all: NN and Hoeffding trees on it as well
         self._plan = None             # ops.serving.ServingPlan of the served pipelines
         self._fam_names: list = []    # latency family of each served pipeline
         self.space = job.space
@@ -245,7 +259,7 @@ class ForecastServer:
         ``_served`` carries (id, output index, False) and ``_spec`` the output range."""
         from omldm_amd.ops.serving import build_plan
 
-        plan = build_plan(pipes, self.space)
+        plan = build_plan(pipes, self.space, nonlinear=self.nonlinear)
         if not plan.served:
             return
         self._plan = plan

@@ -109,10 +109,13 @@ class Job:
         self.fserver = None
         # "plans": the lane as with "true", its wave driven by a serving plan (scaled,
         # polynomial, ORR, MultiClassPA and K-means pipelines on the wave as well)
-        if fs in ("true", "1", "plans") or (fs == "auto" and self.device.type == "cuda"):
+        # "plans-all": "plans" with NN and Hoeffding-tree pipelines on the wave as well
+        if fs in ("true", "1", "plans", "plans-all") or \
+                (fs == "auto" and self.device.type == "cuda"):
             from omldm_amd.engine.forecast_server import ForecastServer
 
-            self.fserver = ForecastServer(self, plans=fs == "plans")
+            self.fserver = ForecastServer(self, plans=fs in ("plans", "plans-all"),
+                                          nonlinear=fs == "plans-all")
         self.ingest = TickIngest([self.train_in] if self.fserver else
                                  [self.train_in, self.fcst_in], cfg.batchSize,
                                  pinned=self.device.type == "cuda",
@@ -241,8 +244,11 @@ class Job:
             msgs = self.request_buffer + list(msgs)
             self.request_buffer = []
         queries = []
+        # (plans-all: an Update can change an NN's activation, a word of its plan entry)
+        kinds = ("Create", "Delete", "Update") if (
+            self.fserver is not None and self.fserver.nonlinear) else ("Create", "Delete")
         moves = self.fserver is not None and any(
-            Request.from_json(robj).request in ("Create", "Delete") for _, _, robj in msgs)
+            Request.from_json(robj).request in kinds for _, _, robj in msgs)
         if moves:
             self.fserver.suspend()  # a Create may grow (move) the model store arena
         for net, dest, robj in msgs:

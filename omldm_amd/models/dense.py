@@ -529,6 +529,28 @@ class NN(Learner):
             return torch.where(out[:, 0] >= 0, 1.0, -1.0)
         return out.argmax(1).float()
 
+    def serving_entry(self, d):
+        # One unit per lane: every width ≤ 64. The batched predict of a bf16-matmul NN rounds
+        # its GEMM operands to bf16, the wave does not — such a network keeps its one-row
+        # predicts. The activation is a word of the entry: an Update that changes it needs
+        # a new plan (engine/job.py reconfigures the forecast server).
+        if d != self.d or max(self.widths) > 64 or (self.act & D.MLP_BF16):
+            return None
+        return {"kind": "mlp", "width": int(self.flat.numel()), "rows": 1, "bias": False,
+                "sign": False, "dense": False,
+                "aux": [len(self.widths) - 1, self.act & 0xFF, self.task_id, *self.widths]}
+
+    def serving_write(self, dst):
+        # per layer the weight block transposed to input-major [in × out] (for a fixed input
+        # the wave's lanes read consecutive floats), then the bias
+        o = 0
+        for a, b in zip(self.widths[:-1], self.widths[1:]):
+            dst[o:o + a * b].view(a, b).copy_(self.flat[o:o + a * b].view(b, a).t(),
+                                              non_blocking=True)
+            dst[o + a * b:o + a * b + b].copy_(self.flat[o + a * b:o + a * b + b],
+                                               non_blocking=True)
+            o += a * b + b
+
     def evaluate(self, batch):
         ok = ~torch.isnan(batch.y)
         if not bool(ok.any()):
@@ -823,6 +845,18 @@ class HT(Learner):
             return D.ht_predict(batch.num, self.Cn, self.depth, self._tree())
         leaf = self._route(batch.num.float())
         return self.cc[leaf].argmax(1).float()
+
+    def serving_entry(self, d):
+        # the wave holds one successor per node in LDS (≤ 1024) and reads a node's class
+        # counts with one lane per class (≤ 32)
+        if d != self.d or self.N > 1024 or self.Cn > 32:
+            return None
+        return {"kind": "tree", "width": self.N * (4 + self.Cn), "rows": 1, "bias": False,
+                "sign": False, "dense": False, "aux": [self.N, self.Cn, max(0, self.depth)]}
+
+    def serving_write(self, dst):
+        # feat, thr, left, right, cc: the head of the state vector, as it lies
+        dst.copy_(self.state[: self.N * (4 + self.Cn)], non_blocking=True)
 
     def evaluate(self, batch):
         ok = ~torch.isnan(batch.y)

@@ -10,8 +10,10 @@ once the copy is complete (engine/forecast_server.py), so an answer never mixes 
 ``PredictServer`` scores hashed-linear rows of one weight matrix. ``PlanServer`` runs the
 same wave from a serving plan (``build_plan``): per pipeline its StandardScaler /
 MinMaxScaler / PolynomialFeatures(2) stages, then a hashed-linear or dense ridge row, a
-MultiClassPA argmax or a K-means argmin, with the parameters in two fp32 arenas that the
-learners and preprocessors fill through their ``serving_write``.
+MultiClassPA argmax or a K-means argmin — and, with ``build_plan(..., nonlinear=True)``, a
+small NN (its forward pass, one unit per lane) or a Hoeffding tree (its walk, through LDS) —
+with the parameters in two fp32 arenas that the learners and preprocessors fill through
+their ``serving_write``.
 """
 from __future__ import annotations
 
@@ -131,11 +133,15 @@ PLAN_WORDS = 128
 PLAN_MAX_MODELS = 60
 PLAN_MAX_STAGES = 4
 PLAN_LANES = 64
-PLAN_KINDS = {"linear": 0, "multiclass": 1, "kmeans": 2}
-PLAN_STAGES = {"affine": 0, "poly2": 1}
+PLAN_KINDS = {"linear": 0, "multiclass": 1, "kmeans": 2, "mlp": 4, "tree": 5}  # (3: none)
+PLAN_NONLINEAR = ("mlp", "tree")   # served only by build_plan(..., nonlinear=True)
+PLAN_MLP_MAX_LAYERS, PLAN_MLP_MAX_WIDTH = 4, 64
+PLAN_TREE_MAX_NODES, PLAN_TREE_MAX_CLASSES = 1024, 32
+PLAN_STAGES = {"affine": 0, "poly2": 1, "poly2_lazy": 2}
 PLAN_BIAS, PLAN_SIGN, PLAN_DENSE = 1, 2, 4
 PL_KIND, PL_OUT, PL_STAGES, PL_FLAGS, PL_OFF, PL_WIDTH, PL_K, PL_STAGE0, PL_PAIRS = \
     0, 1, 2, 3, 4, 5, 6, 8, 64
+PL_AUX = 24  # mlp: L, act, task, w_0..w_L; tree: N, C, depth
 PLAN_ERRORS = {-10: "shape", -11: "more than 64 lanes", -12: "stages", -13: "arena extent",
                -14: "output index", -15: "pair table"}
 
@@ -165,15 +171,17 @@ class ServingPlan:
             writer.serving_write(arena[off:off + n])
 
 
-def _plan_entry(pipe, space, out: int, off: int):
+def _plan_entry(pipe, space, out: int, off: int, nonlinear: bool = False):
     """(entry words, regions, arena end) of one pipeline, or None when the wave cannot
     serve it: an unknown learner or preprocessor, more than PLAN_MAX_STAGES stages, or more
-    than PLAN_LANES lanes (dense width after the stages + categorical fields + bias)."""
+    than PLAN_LANES lanes (dense width after the stages + categorical fields + bias). An
+    MLP or a tree (NN, HT) is an entry only with ``nonlinear``."""
     pres = list(pipe.preprocessors)
     if len(pres) > PLAN_MAX_STAGES:
         return None
     e = np.zeros(PLAN_WORDS, dtype=np.int32)
     regions, npairs, d = [], 0, space.dn
+    lane_d = None  # the lane width in front of a lazy poly2 stage (else: d)
     for s, p in enumerate(pres):
         st = p.serving_stage(d) if hasattr(p, "serving_stage") else None
         if st is None:
@@ -187,16 +195,32 @@ def _plan_entry(pipe, space, out: int, off: int):
         else:  # poly2: the static pair table, in PolynomialFeatures._index order
             pairs = p.pair_index(d, "cpu").tolist()
             if d + len(pairs) > PLAN_LANES or npairs + len(pairs) > PLAN_WORDS - PL_PAIRS:
-                return None
+                # too wide for the lanes or the pair table. A tree reads one feature per
+                # node, so as the LAST stage in front of one the map is not laid out at all:
+                # the wave takes a node's product from its two lanes (kPlanPoly2Lazy)
+                ent = pipe.learner.serving_entry(d + len(pairs)) \
+                    if hasattr(pipe.learner, "serving_entry") else None
+                if not (nonlinear and s == len(pres) - 1 and ent is not None
+                        and ent["kind"] == "tree" and 1 <= d <= PLAN_LANES):
+                    return None
+                e[w:w + 4] = (PLAN_STAGES["poly2_lazy"], 0, 0, d)
+                lane_d = d
+                d += len(pairs)
+                continue
             e[w:w + 4] = (PLAN_STAGES[kind], npairs, 0, d)
             for a, b in pairs:
                 e[PL_PAIRS + npairs] = int(a) | (int(b) << 8)
                 npairs += 1
             d += len(pairs)
     ent = pipe.learner.serving_entry(d) if hasattr(pipe.learner, "serving_entry") else None
-    if ent is None:
+    if ent is None or (ent["kind"] in PLAN_NONLINEAR and not nonlinear):
         return None
-    if ent["kind"] == "kmeans":
+    if ent["kind"] in PLAN_NONLINEAR:
+        lanes = d if lane_d is None else lane_d
+        if not _aux_fits(ent):
+            return None
+        e[PL_AUX:PL_AUX + len(ent["aux"])] = ent["aux"]
+    elif ent["kind"] == "kmeans":
         lanes = d
     else:
         lanes = d + (0 if ent["dense"] else space.dc) + int(ent["bias"])
@@ -213,15 +237,31 @@ def _plan_entry(pipe, space, out: int, off: int):
     return e, regions, off + floats
 
 
-def build_plan(pipes, space) -> ServingPlan:
+def _aux_fits(ent) -> bool:
+    """The limits plan_check puts on an mlp / tree entry (serve_plan.h)."""
+    aux = [int(v) for v in ent["aux"]]
+    if ent["kind"] == "mlp":
+        L, widths = aux[0], aux[3:]
+        return (1 <= L <= PLAN_MLP_MAX_LAYERS and len(widths) == L + 1 and 0 <= aux[1] <= 3
+                and 0 <= aux[2] <= 2 and all(1 <= w <= PLAN_MLP_MAX_WIDTH for w in widths)
+                and ent["width"] == sum(a * b + b for a, b in zip(widths[:-1], widths[1:])))
+    N, C, depth = aux
+    return (1 <= N <= PLAN_TREE_MAX_NODES and 2 <= C <= PLAN_TREE_MAX_CLASSES and depth >= 0
+            and ent["width"] == N * (4 + C))
+
+
+def build_plan(pipes, space, nonlinear: bool = False) -> ServingPlan:
     """The serving plan over ``pipes`` (objects with ``id``, ``preprocessors``, ``learner``):
     hashed-linear learners, ORR, MultiClassPA and K-means behind StandardScaler /
     MinMaxScaler / PolynomialFeatures(2) stages that fit the wave's limits are served, the
-    first PLAN_MAX_MODELS of them; every other pipeline is left direct. Pure Python."""
+    first PLAN_MAX_MODELS of them; every other pipeline is left direct. ``nonlinear``: NN
+    (≤ 4 layers of ≤ 64 units, fp32 matmul) and Hoeffding trees (≤ 1024 nodes, ≤ 32 classes)
+    are served as well, as ``mlp`` / ``tree`` entries; a tree directly behind a
+    PolynomialFeatures(2) too wide for the lanes takes it as a lazy stage. Pure Python."""
     entries, regions, served, direct, off = [], [], [], [], 0
     fits = space.dn + space.dc <= PLAN_LANES - 3  # the request line's payload
     for pipe in pipes:
-        got = _plan_entry(pipe, space, len(served), off) \
+        got = _plan_entry(pipe, space, len(served), off, nonlinear) \
             if fits and len(served) < PLAN_MAX_MODELS else None
         if got is None:
             direct.append(pipe)

@@ -79,6 +79,7 @@ class JobConfig:
     ingestCopy: str = "pull"              # GPU staging copy: pull (kernel) | sdma (hipMemcpyAsync)
     forecastServer: str = "auto"          # per-record forecasts on the resident serving wave (auto: GPU);
                                           # plans: the plan-driven wave (scalers, poly2, ORR, MultiClassPA, K-means)
+                                          # plans-all: plans, with NN and Hoeffding trees on the wave as well
     pipelineStreams: int = 8              # GPU: pipelines of a tick train on up to this many streams
     fusePipelines: str = "true"           # GPU: hashed-linear pipelines sharing a prep: one launch
     routeAhead: str = "false"             # GPU: holdout route + v3 prep beside the previous round
