@@ -921,12 +921,477 @@ __global__ __launch_bounds__(256) void mlp_colsum_kernel(const float* __restrict
   if (t != 0.f) atomicAdd(&dacc[c], t);
 }
 
+// ------------------------------------------------------------------ streamed-weight form
+// Layer stacks whose weights do not fit one CU's LDS (128-wide hidden layers and up). The
+// same 32-row mini-batch SGD, one workgroup (16 waves) per spoke, but the spoke's working
+// model is its row of the S × nparams scratch `ws` in HBM (L2-resident in practice): copied
+// from w at round start, trained in place, turned into W_spoke − w at round end, where
+// mlp_colsum_kernel folds the rows into dacc as for the fused forms. LDS holds only the
+// mini-batch: H_0..H_L, the layer-output gradients G_1..G_L, the biases and y.
+// * forward and dH: each wave owns 16×16 output tiles; the activation / gradient operand
+//   comes from LDS, the weight operand straight from the slab (forward: a weight row is
+//   k-contiguous, 16 bytes per lane and k step; dH: the tile's 16 columns are contiguous
+//   across lanes). The slab is the flat, unpadded parameter layout, so loads are masked to
+//   the real rows and columns (padding reads as zero) and carry 4-byte alignment only;
+// * update W_l −= η·G_{l+1}ᵀ·H_l: both operands from LDS, the read-modify-write of the slab
+//   straight from the MFMA accumulators (one owner lane per weight);
+// * biases and their gradients (column sums of G) stay in LDS.
+// Why workgroup scope suffices: a slab row is written and read by ONE workgroup, hence on
+// ONE CU, through that CU's vector L1 (write-through: a store updates the line there and
+// goes on to L2). Every slab hand-off between waves is store → __syncthreads() → load; the
+// barrier's workgroup-scope release/acquire waits for the stores (vmcnt(0)) before any
+// wave passes it, and no other CU's L1 ever holds or needs these lines inside the launch.
+// Nothing crosses workgroups before the kernel boundary (w is read-only here; the colsum
+// pass is a later launch), so there are no flags, spins or agent-scope fences.
+struct MlpStreamDesc {
+  int L, task, K, act, bf16;
+  int n[kMaxLayers + 1], np[kMaxLayers + 1];  // widths, and padded to 16
+  int woff[kMaxLayers], boff[kMaxLayers];     // flat parameter layout (= slab layout)
+  int lh[kMaxLayers + 1], ldh[kMaxLayers + 1];  // LDS: H_l, row stride (also G_l's)
+  int lg[kMaxLayers + 1];                       // LDS: G_l, l = 1..L
+  int lb[kMaxLayers];                           // LDS: b_l, np[l+1] floats
+  int ly, fwd_total, total;                     // floats: forward kernel / round kernel
+};
+
+struct __attribute__((packed, aligned(4))) SlabVec4 {
+  float v[4];
+};
+
+// row[k..k+3] of an n-float slab row; zero past n or when the row itself is padding
+__device__ __forceinline__ void slab_ld4(const float* row, int k, int n, bool ok, float (&o)[4]) {
+  if (ok && k + 3 < n) {
+    const SlabVec4 t = *reinterpret_cast<const SlabVec4*>(row + k);
+    o[0] = t.v[0]; o[1] = t.v[1]; o[2] = t.v[2]; o[3] = t.v[3];
+  } else {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) o[u] = (ok && k + u < n) ? row[k + u] : 0.f;
+  }
+}
+
+template <bool BF16>
+__device__ __forceinline__ f32x4 mfma16_step(const float (&av)[4], const float (&bv)[4], f32x4 acc) {
+  if constexpr (BF16) {
+    const bf16x4 af = {bf16_bits(av[0]), bf16_bits(av[1]), bf16_bits(av[2]), bf16_bits(av[3])};
+    const bf16x4 bfv = {bf16_bits(bv[0]), bf16_bits(bv[1]), bf16_bits(bv[2]), bf16_bits(bv[3])};
+    acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(af, bfv, acc, 0, 0, 0);
+  } else {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
+  }
+  return acc;
+}
+
+// Both 16-row tiles of the mini-batch against one 16-column weight tile, so a weight
+// fragment is loaded once: c0 / c1 = A[0..15 / 16..31]·Wtᵀ with A(i, k) = a[i·lda + k] in
+// LDS and Wt = 16 slab rows of n_in floats, of which the first `rows` exist. K = padded
+// n_in. Operand map and accumulator layout of gemm16t. The k steps whose 16 columns all
+// exist load unconditionally (a padding row re-reads row 0 and is zeroed by a select) and
+// are unrolled, so several steps' loads are in flight; the last, partial step is masked.
+template <bool BF16>
+__device__ __forceinline__ void stream_gemm_fwd(const float* a, int lda, const float* wt, int n_in,
+                                                int rows, int K, f32x4& c0, f32x4& c1) {
+  const int lane = threadIdx.x & 63;
+  const int r = lane & 15, g = lane >> 4;
+  c0 = f32x4{0.f, 0.f, 0.f, 0.f};
+  c1 = c0;
+  const float* ap0 = a + r * lda + 4 * g;
+  const float* ap1 = ap0 + 16 * lda;
+  const bool ok = r < rows;
+  const float* brow = wt + (size_t)(ok ? r : 0) * n_in;
+  const int Kf = n_in & ~15;
+  auto step = [&](int k, const float (&bv)[4]) {
+    float a0[4], a1[4];
+    const float4 t0 = *reinterpret_cast<const float4*>(ap0 + k);
+    const float4 t1 = *reinterpret_cast<const float4*>(ap1 + k);
+    a0[0] = t0.x; a0[1] = t0.y; a0[2] = t0.z; a0[3] = t0.w;
+    a1[0] = t1.x; a1[1] = t1.y; a1[2] = t1.z; a1[3] = t1.w;
+    c0 = mfma16_step<BF16>(a0, bv, c0);
+    c1 = mfma16_step<BF16>(a1, bv, c1);
+  };
+  int k = 0;
+  for (; k + 64 <= Kf; k += 64) {  // four k steps' loads issued ahead of their MFMAs
+    SlabVec4 t[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) t[s] = *reinterpret_cast<const SlabVec4*>(brow + k + 16 * s + 4 * g);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const float bv[4] = {ok ? t[s].v[0] : 0.f, ok ? t[s].v[1] : 0.f, ok ? t[s].v[2] : 0.f,
+                           ok ? t[s].v[3] : 0.f};
+      step(k + 16 * s, bv);
+    }
+  }
+  for (; k < Kf; k += 16) {
+    const SlabVec4 t = *reinterpret_cast<const SlabVec4*>(brow + k + 4 * g);
+    const float bv[4] = {ok ? t.v[0] : 0.f, ok ? t.v[1] : 0.f, ok ? t.v[2] : 0.f, ok ? t.v[3] : 0.f};
+    step(k, bv);
+  }
+  if (Kf < K) {
+    float bv[4];
+    slab_ld4(brow, Kf + 4 * g, n_in, ok, bv);
+    step(Kf, bv);
+  }
+}
+
+// c0 / c1 = A[0..15 / 16..31]·W[:, cb..cb+15]: A(i, k) = a[i·lda + k] in LDS (k over the
+// layer's outputs), W the layer's n_out × n_in slab block. K = padded n_out. The tile's 16
+// columns are contiguous across lanes; a padding column re-reads column 0 and is zeroed.
+template <bool BF16>
+__device__ __forceinline__ void stream_gemm_bwd(const float* a, int lda, const float* W, int n_in,
+                                                int n_out, int cb, int K, f32x4& c0, f32x4& c1) {
+  const int lane = threadIdx.x & 63;
+  const int r = lane & 15, g = lane >> 4;
+  c0 = f32x4{0.f, 0.f, 0.f, 0.f};
+  c1 = c0;
+  const float* ap0 = a + r * lda + 4 * g;
+  const float* ap1 = ap0 + 16 * lda;
+  const int j = cb + r;
+  const bool ok = j < n_in;
+  const float* bp = W + (size_t)(4 * g) * n_in + (ok ? j : 0);
+  const int Kf = n_out & ~15;
+  auto step = [&](int k, const float (&bv)[4]) {
+    float a0[4], a1[4];
+    const float4 t0 = *reinterpret_cast<const float4*>(ap0 + k);
+    const float4 t1 = *reinterpret_cast<const float4*>(ap1 + k);
+    a0[0] = t0.x; a0[1] = t0.y; a0[2] = t0.z; a0[3] = t0.w;
+    a1[0] = t1.x; a1[1] = t1.y; a1[2] = t1.z; a1[3] = t1.w;
+    c0 = mfma16_step<BF16>(a0, bv, c0);
+    c1 = mfma16_step<BF16>(a1, bv, c1);
+  };
+  int k = 0;
+  for (; k + 32 <= Kf; k += 32) {  // two k steps' loads issued ahead of their MFMAs
+    float t[2][4];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) t[s][u] = bp[(size_t)(k + 16 * s + u) * n_in];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const float bv[4] = {ok ? t[s][0] : 0.f, ok ? t[s][1] : 0.f, ok ? t[s][2] : 0.f,
+                           ok ? t[s][3] : 0.f};
+      step(k + 16 * s, bv);
+    }
+  }
+  for (; k < Kf; k += 16) {
+    float bv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float t = bp[(size_t)(k + u) * n_in];
+      bv[u] = ok ? t : 0.f;
+    }
+    step(k, bv);
+  }
+  if (Kf < K) {
+    float bv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int kk = Kf + 4 * g + u;
+      bv[u] = (ok && kk < n_out) ? W[(size_t)kk * n_in + j] : 0.f;
+    }
+    step(Kf, bv);
+  }
+}
+
+// One layer of a staged 32-row tile: Ho = act(H·Wᵀ + b) (no activation on the output
+// layer); padding columns of Ho stay exactly zero. `bias` holds n_out floats. A wave takes
+// a 16-column tile of the layer's outputs for all 32 rows.
+template <bool BF16>
+__device__ __forceinline__ void stream_layer_fwd(const float* H, int ldh, float* Ho, int ldo,
+                                                 const float* W, const float* bias, int n_in,
+                                                 int np_in, int n_out, int np_out, bool hidden,
+                                                 int act) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+  const int ci = lane & 15, cg = lane >> 4;
+  for (int ct = wave; ct < np_out / 16; ct += nw) {
+    f32x4 c0, c1;
+    stream_gemm_fwd<BF16>(H, ldh, W + (size_t)ct * 16 * n_in, n_in, n_out - ct * 16, np_in, c0, c1);
+    const int col = ct * 16 + ci;
+    const bool pad = col >= n_out;
+    const float b = pad ? 0.f : bias[col];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float v0 = c0[q] + b, v1 = c1[q] + b;
+      if (hidden) {
+        v0 = act_fwd(v0, act);
+        v1 = act_fwd(v1, act);
+      }
+      Ho[(4 * cg + q) * ldo + col] = pad ? 0.f : v0;
+      Ho[(16 + 4 * cg + q) * ldo + col] = pad ? 0.f : v1;
+    }
+  }
+}
+
+__device__ __forceinline__ void stream_stage(const float* __restrict__ x, long long r0, long long r1,
+                                             float* H, int n0, int np0, int ld) {
+  for (int i = threadIdx.x; i < kMB * np0; i += blockDim.x) {
+    const int r = i / np0, c = i - r * np0;
+    const long long row = r0 + r;
+    H[r * ld + c] = (row < r1 && c < n0) ? x[row * n0 + c] : 0.f;
+  }
+}
+
+constexpr int kStreamWaves = 16;
+
+// The barrier behind slab stores: every storing wave first waits until its stores have
+// left for L2 through this CU's L1 (vmcnt(0)), so the loads of any wave past the barrier
+// find them; __syncthreads() orders the LDS side.
+__device__ __forceinline__ void slab_barrier() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(kStreamWaves * 64) void mlp_round_stream_kernel(
+    const float* __restrict__ w, const float* __restrict__ x, const float* __restrict__ yv,
+    long long B, int R, float lr, float* __restrict__ stats, float* __restrict__ nact,
+    MlpStreamDesc g, float* ws, int nparams) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  constexpr int NT = kStreamWaves * 64;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int ci = lane & 15, cg = lane >> 4;
+  float* slab = ws + (size_t)blockIdx.x * nparams;
+  const long long r0 = (long long)blockIdx.x * R;
+  const long long r1 = min(B, r0 + R);
+  if (r0 >= B) {  // a spoke without rows: a zero delta for the column sums
+    for (int i = tid; i < nparams; i += NT) slab[i] = 0.f;
+    return;
+  }
+  const int L = g.L, npL = g.np[L];
+  for (int i = tid; i < nparams; i += NT) slab[i] = w[i];
+  for (int l = 0; l < L; ++l)
+    for (int o = tid; o < g.np[l + 1]; o += NT)
+      sm[g.lb[l] + o] = o < g.n[l + 1] ? w[g.boff[l] + o] : 0.f;
+  slab_barrier();
+  float loss = 0.f, corr = 0.f, nv = 0.f;
+  for (long long m0 = r0; m0 < r1; m0 += kMB) {
+    stream_stage(x, m0, r1, sm + g.lh[0], g.n[0], g.np[0], g.ldh[0]);
+    if (tid < kMB) {
+      const long long row = m0 + tid;
+      sm[g.ly + tid] = row < r1 ? yv[row] : __builtin_nanf("");
+    }
+    __syncthreads();
+    const float yl = sm[g.ly + (lane & 31)];
+    const int cnt = __builtin_popcountll(__builtin_amdgcn_ballot_w64(lane < 32 && yl == yl));
+    if (cnt == 0) {
+      __syncthreads();  // every wave has read y before the next step restages it
+      continue;
+    }
+    const float eta = lr / (float)cnt;
+    // ---- forward
+    for (int l = 0; l < L; ++l) {
+      const float* W = slab + g.woff[l];
+      if (g.bf16)
+        stream_layer_fwd<true>(sm + g.lh[l], g.ldh[l], sm + g.lh[l + 1], g.ldh[l + 1], W,
+                               sm + g.lb[l], g.n[l], g.np[l], g.n[l + 1], g.np[l + 1], l + 1 < L,
+                               g.act);
+      else
+        stream_layer_fwd<false>(sm + g.lh[l], g.ldh[l], sm + g.lh[l + 1], g.ldh[l + 1], W,
+                                sm + g.lb[l], g.n[l], g.np[l], g.n[l + 1], g.np[l + 1], l + 1 < L,
+                                g.act);
+      __syncthreads();
+    }
+    // ---- loss gradient G_L: one thread per row, a serial pass over the row's logits in
+    // LDS (any output width; the rules of mlp_round_kernel)
+    if (tid < kMB) {
+      const float y = sm[g.ly + tid];
+      const float* o = sm + g.lh[L] + tid * g.ldh[L];
+      float* G = sm + g.lg[L] + tid * g.ldh[L];
+      for (int k = 0; k < npL; ++k) G[k] = 0.f;
+      if (y == y) {
+        if (g.task == 0) {
+          const float e = o[0] - y;
+          G[0] = 2.f * e;
+          loss += e * e;
+        } else if (g.task == 1) {
+          const float t = y > 0.f ? 1.f : 0.f, z = o[0];
+          G[0] = 1.f / (1.f + __expf(-z)) - t;
+          loss += fmaxf(z, 0.f) - z * t + log1pf(__expf(-fabsf(z)));
+          corr += ((z >= 0.f) == (t > 0.f)) ? 1.f : 0.f;
+        } else {
+          int yi = (int)y;
+          yi = yi < 0 ? 0 : (yi >= g.K ? g.K - 1 : yi);
+          float m = o[0];
+          int am = 0;
+          for (int k = 1; k < g.K; ++k)
+            if (o[k] > m) {
+              m = o[k];
+              am = k;
+            }
+          float se = 0.f;
+          for (int k = 0; k < g.K; ++k) se += __expf(o[k] - m);
+          const float inv = 1.f / se;
+          for (int k = 0; k < g.K; ++k) G[k] = __expf(o[k] - m) * inv - (k == yi ? 1.f : 0.f);
+          loss += -(o[yi] - m - __logf(se));
+          corr += am == yi ? 1.f : 0.f;
+        }
+        nv += 1.f;
+      }
+    }
+    __syncthreads();
+    // ---- backward, per layer: dH_l from the slab's W_l, barrier, then W_l and b_l updated
+    for (int l = L - 1; l >= 0; --l) {
+      const float* Gc = sm + g.lg[l + 1];
+      const int ldg = g.ldh[l + 1];
+      const float* H = sm + g.lh[l];
+      const int ldh = g.ldh[l], n_in = g.n[l], n_out = g.n[l + 1];
+      float* W = slab + g.woff[l];
+      if (l > 0) {  // G_l = (G_{l+1} · W_l) ⊙ act'(H_l)
+        float* Gn = sm + g.lg[l];
+        for (int ct = wave; ct < g.np[l] / 16; ct += kStreamWaves) {
+          f32x4 c0, c1;
+          if (g.bf16)
+            stream_gemm_bwd<true>(Gc, ldg, W, n_in, n_out, ct * 16, g.np[l + 1], c0, c1);
+          else
+            stream_gemm_bwd<false>(Gc, ldg, W, n_in, n_out, ct * 16, g.np[l + 1], c0, c1);
+          const int col = ct * 16 + ci;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int row = 4 * cg + q;
+            Gn[row * ldh + col] = c0[q] * act_grad(H[row * ldh + col], g.act);
+            Gn[(row + 16) * ldh + col] = c1[q] * act_grad(H[(row + 16) * ldh + col], g.act);
+          }
+        }
+        __syncthreads();  // W_l fully read before it is updated
+      }
+      // the tile's old weights are requested first and arrive while the product is formed
+      const int ntc = g.np[l] / 16, nto = g.np[l + 1] / 16;
+      for (int t = wave; t < nto * ntc; t += kStreamWaves) {
+        const int to = t / ntc, tc = t - to * ntc;
+        const int c = tc * 16 + ci, o0 = to * 16 + 4 * cg;
+        float* Wp = W + (size_t)o0 * n_in + c;
+        float old[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) old[q] = (c < n_in && o0 + q < n_out) ? Wp[(size_t)q * n_in] : 0.f;
+        const f32x4 acc = gemm16p<false, false>(Gc + to * 16, 1, ldg, H + tc * 16, ldh, 1, kMB, g.bf16);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (c < n_in && o0 + q < n_out) Wp[(size_t)q * n_in] = old[q] - eta * acc[q];
+      }
+      for (int o = tid; o < n_out; o += NT) {
+        float s = 0.f;
+        for (int i = 0; i < kMB; ++i) s += Gc[i * ldg + o];
+        sm[g.lb[l] + o] -= eta * s;
+      }
+      slab_barrier();
+    }
+  }
+  // ---- round end: the slab row becomes Δ = W_spoke − W_0 (every step ended in a barrier)
+  for (int l = 0; l < L; ++l) {
+    const int nw = g.n[l + 1] * g.n[l];
+    for (int i = tid; i < nw; i += NT) slab[g.woff[l] + i] -= w[g.woff[l] + i];
+    for (int o = tid; o < g.n[l + 1]; o += NT)
+      slab[g.boff[l] + o] = sm[g.lb[l] + o] - w[g.boff[l] + o];
+  }
+  if (wave == 0) {
+    loss = wave_sum(loss);
+    corr = wave_sum(corr);
+    nv = wave_sum(nv);
+    if (lane == 0 && nv > 0.f) {
+      atomicAdd(&stats[0], loss);
+      atomicAdd(&stats[1], nv);
+      atomicAdd(&stats[2], corr);
+      atomicAdd(&stats[3], 1.f);
+      if (nact) atomicAdd(nact, 1.f);
+    }
+  }
+}
+
+// Inference at the same widths: 32-row tiles grid-stride, activations in LDS, weights and
+// biases read from w itself (read-only, shared by every workgroup).
+constexpr int kStreamFwdWaves = 8;
+__global__ __launch_bounds__(kStreamFwdWaves * 64) void mlp_forward_stream_kernel(
+    const float* __restrict__ w, const float* __restrict__ x, long long B,
+    float* __restrict__ out, MlpStreamDesc g) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int L = g.L;
+  for (long long m0 = (long long)blockIdx.x * kMB; m0 < B; m0 += (long long)gridDim.x * kMB) {
+    __syncthreads();  // previous tile's H_L consumed
+    stream_stage(x, m0, B, sm + g.lh[0], g.n[0], g.np[0], g.ldh[0]);
+    __syncthreads();
+    for (int l = 0; l < L; ++l) {
+      if (g.bf16)
+        stream_layer_fwd<true>(sm + g.lh[l], g.ldh[l], sm + g.lh[l + 1], g.ldh[l + 1],
+                               w + g.woff[l], w + g.boff[l], g.n[l], g.np[l], g.n[l + 1],
+                               g.np[l + 1], l + 1 < L, g.act);
+      else
+        stream_layer_fwd<false>(sm + g.lh[l], g.ldh[l], sm + g.lh[l + 1], g.ldh[l + 1],
+                                w + g.woff[l], w + g.boff[l], g.n[l], g.np[l], g.n[l + 1],
+                                g.np[l + 1], l + 1 < L, g.act);
+      __syncthreads();
+    }
+    const float* o = sm + g.lh[L];
+    for (int i = threadIdx.x; i < kMB * g.K; i += blockDim.x) {
+      const int r = i / g.K, k = i - r * g.K;
+      if (m0 + r < B) out[(m0 + r) * g.K + k] = o[r * g.ldh[L] + k];
+    }
+  }
+}
+
+// LDS layout of the streamed form. Gradient buffers: one per layer output (G_1..G_L), or
+// two max-width buffers that layers of equal parity share (only G_{l+1} and G_l are live
+// together) — whichever is smaller, so the form admits the union of both sets
+// ([13, 512, 1] needs the first, deep equal-width stacks gain from the second).
+static int make_stream_desc(int L, const int* widths, int task, int act, MlpStreamDesc* g) {
+  if (L < 1 || L > kMaxLayers || (act & 0xff) > kIdentity || (act & ~0x1ff)) return -1;
+  *g = MlpStreamDesc{};
+  g->L = L;
+  g->task = task;
+  g->act = act & 0xff;
+  g->bf16 = (act >> 8) & 1;
+  g->K = widths[L];
+  long long off = 0;
+  for (int l = 0; l <= L; ++l) {
+    if (widths[l] < 1 || widths[l] > (1 << 15)) return -1;
+    g->n[l] = widths[l];
+    g->np[l] = (widths[l] + 15) / 16 * 16;
+  }
+  for (int l = 0; l < L; ++l) {
+    g->woff[l] = (int)off;
+    off += (long long)g->n[l + 1] * g->n[l];
+    g->boff[l] = (int)off;
+    off += g->n[l + 1];
+    if (off > (1ll << 30)) return -1;
+  }
+  long long p = 0, per = 0;
+  int maxld = 0;
+  for (int l = 0; l <= L; ++l) {
+    g->ldh[l] = g->np[l] + 4;
+    g->lh[l] = (int)p;
+    p += kMB * g->ldh[l];
+    if (l >= 1) {
+      per += kMB * g->ldh[l];
+      if (g->ldh[l] > maxld) maxld = g->ldh[l];
+    }
+  }
+  g->fwd_total = (int)p;
+  for (int l = 0; l < L; ++l) {
+    g->lb[l] = (int)p;
+    p += g->np[l + 1];
+  }
+  const long long rot = 2ll * kMB * maxld;
+  if (per <= rot) {
+    for (int l = 1; l <= L; ++l) {
+      g->lg[l] = (int)p;
+      p += kMB * g->ldh[l];
+    }
+  } else {
+    for (int l = 1; l <= L; ++l) g->lg[l] = (int)(p + (l & 1) * kMB * maxld);
+    p += rot;
+  }
+  g->ly = (int)p;
+  p += kMB;
+  if (p > (1ll << 28)) return -1;
+  g->total = (int)p;
+  return 0;
+}
+
 }  // namespace omldm
 
 using namespace omldm;
 
 // Round kernel form: 0 v1 (mlp_round_kernel), 1 / 2 / 3 v2 with 4 / 8 / 16 waves (v2 takes
-// output widths ≤ 16). `set` ≥ 0 sets it; the default comes from OMLDM_MLP_FORM (3).
+// output widths ≤ 16), 4 the streamed-weight form at every shape it takes, also where a fused
+// form fits (tests and benchmarks; it applies to omldm_mlp_forward too). Whatever the form, a
+// stack no fused kernel holds goes to the streamed form. `set` ≥ 0 sets it; the default
+// comes from OMLDM_MLP_FORM (3).
 OMLDM_API int omldm_mlp_form(int set) {
   static int form = [] {
     const char* e = getenv("OMLDM_MLP_FORM");
@@ -943,12 +1408,41 @@ OMLDM_API long long omldm_mlp_lds_bytes(int L, const int* widths) {
   return (long long)g.total * 4;
 }
 
+// LDS bytes of the streamed-weight form (mini-batch activations and gradients only).
+OMLDM_API long long omldm_mlp_stream_lds_bytes(int L, const int* widths) {
+  MlpStreamDesc g;
+  if (make_stream_desc(L, widths, 0, 0, &g)) return -1;
+  return (long long)g.total * 4;
+}
+
+constexpr size_t kMlpLdsMax = 160 * 1024;
+
+static int launch_round_stream(const float* w, const float* x, const float* y, long long B, int R,
+                               int S, int L, const int* widths, int task, int act, float lr,
+                               float* dacc, float* stats, float* nact, float* ws,
+                               hipStream_t stream) {
+  MlpStreamDesc g;
+  if (make_stream_desc(L, widths, task, act, &g)) return -1;
+  const size_t lds = (size_t)g.total * 4;
+  if (lds > kMlpLdsMax) return -2;
+  if (!ws) return -4;  // the working models live in the scratch rows
+  const int e = check_dyn_lds((const void*)mlp_round_stream_kernel, lds);
+  if (e) return e;
+  const int nparams = g.boff[L - 1] + g.n[L];
+  hipLaunchKernelGGL(mlp_round_stream_kernel, dim3(S), dim3(kStreamWaves * 64), lds, stream, w, x,
+                     y, B, R, lr, stats, nact, g, ws, nparams);
+  hipLaunchKernelGGL(mlp_colsum_kernel, dim3((nparams + 255) / 256, (S + kMlpSlab - 1) / kMlpSlab),
+                     dim3(256), 0, stream, ws, S, nparams, dacc);
+  return (int)hipGetLastError();
+}
+
 // One protocol round: S spokes × R rows (spoke s owns rows [sR, sR+R)); task 0 regression,
 // 1 binary logistic, 2 softmax. dacc[nparams] += Σ_s Δ_s; stats[0..3] += loss, n, correct,
 // active spokes (spokes with ≥ 1 labelled row); nact (optional, zeroed beforehand) += active
 // spokes too. Follow with omldm_multiclass_apply(w, dacc, nparams, ..., nact, ...): the
 // apply kernel clears stats, so its divisor must live in a separate buffer.
-// ws: optional S × nparams scratch (spoke deltas by plain stores + slab column sums).
+// ws: optional S × nparams scratch (spoke deltas by plain stores + slab column sums); the
+// streamed-weight form (stacks past the fused kernels' LDS) requires it: -4 without.
 OMLDM_API int omldm_mlp_round(const float* w, const float* x, const float* y, long long B, int R,
                               int S, int L, const int* widths, int task, int act, float lr,
                               float* dacc, float* stats, float* nact, float* ws, void* stream) {
@@ -956,6 +1450,9 @@ OMLDM_API int omldm_mlp_round(const float* w, const float* x, const float* y, lo
   if (R <= 0 || (long long)R * S < B) return -3;
   MlpDesc g;
   const int form = omldm_mlp_form(-1);
+  if (form == 4)
+    return launch_round_stream(w, x, y, B, R, S, L, widths, task, act, lr, dacc, stats, nact, ws,
+                               (hipStream_t)stream);
   if (form > 0 && widths[L] <= 16 && make_desc(L, widths, task, act, &g, 16) == 0 &&
       (size_t)g.total * 4 <= 160 * 1024) {
     const size_t lds = (size_t)g.total * 4;
@@ -977,7 +1474,9 @@ OMLDM_API int omldm_mlp_round(const float* w, const float* x, const float* y, lo
   } else {
     if (make_desc(L, widths, task, act, &g)) return -1;
     const size_t lds = (size_t)g.total * 4;
-    if (lds > 160 * 1024) return -2;
+    if (lds > 160 * 1024)
+      return launch_round_stream(w, x, y, B, R, S, L, widths, task, act, lr, dacc, stats, nact, ws,
+                                 (hipStream_t)stream);
     int e = check_dyn_lds((const void*)mlp_round_kernel, lds);
     if (e) return e;
     const int nparams = g.boff[g.L - 1] + g.n[g.L];
@@ -997,11 +1496,21 @@ OMLDM_API int omldm_mlp_forward(const float* w, const float* x, long long B, int
   MlpDesc g;
   if (make_desc(L, widths, 0, act, &g)) return -1;
   const size_t lds = (size_t)g.total * 4;
-  if (lds > 160 * 1024) return -2;
-  int e = check_dyn_lds((const void*)mlp_forward_kernel, lds);
-  if (e) return e;
   long long tiles = (B + kMB - 1) / kMB;
   int blocks = (int)(tiles < 1024 ? tiles : 1024);
+  if (lds > 160 * 1024 || omldm_mlp_form(-1) == 4) {  // streamed weights
+    MlpStreamDesc sg;
+    if (make_stream_desc(L, widths, 0, act, &sg)) return -1;
+    const size_t slds = (size_t)sg.fwd_total * 4;
+    if ((size_t)sg.total * 4 > kMlpLdsMax) return -2;  // one limit for training and scoring
+    int e = check_dyn_lds((const void*)mlp_forward_stream_kernel, slds);
+    if (e) return e;
+    hipLaunchKernelGGL(mlp_forward_stream_kernel, dim3(blocks), dim3(kStreamFwdWaves * 64), slds,
+                       (hipStream_t)stream, w, x, B, out, sg);
+    return (int)hipGetLastError();
+  }
+  int e = check_dyn_lds((const void*)mlp_forward_kernel, lds);
+  if (e) return e;
   hipLaunchKernelGGL(mlp_forward_kernel, dim3(blocks), dim3(256), lds, (hipStream_t)stream, w, x,
                      B, out, g);
   return (int)hipGetLastError();

@@ -425,12 +425,15 @@ class NN(Learner):
     reference's DL4J MultiLayerNetwork path (hs_err_pid77107.log:97-110).
 
     A round runs S virtual spokes (one workgroup each, csrc/kernels/mlp.hip): spoke s does
-    32-row mini-batch SGD over its rows from the round-start model entirely in LDS on the
-    fp32 matrix cores; the spokes' models are then averaged (intra-GPU hub). Parameters
+    32-row mini-batch SGD over its rows from the round-start model on the fp32 matrix
+    cores — entirely in LDS while the padded model fits there (e.g. [13, 64, 64, 1]), else
+    with the working model streamed from HBM and only the mini-batch in LDS (128-wide hidden
+    layers and up); the spokes' models are then averaged (intra-GPU hub). Parameters
     live in ONE flat fp32 buffer (W_0, b_0, W_1, b_1, … row-major) — the protocols' state
     vector. Loss: squared error (task=regression), logistic (nClasses ≤ 1, labels ±1 or
-    {0,1}) or softmax cross-entropy (nClasses = K ≥ 2). At most 4 layers whose padded
-    widths fit the 160 KB LDS of a CU (e.g. 128-wide hidden layers)."""
+    {0,1}) or softmax cross-entropy (nClasses = K ≥ 2). At most 4 layers; on a GPU a
+    32-row mini-batch's activations and gradients must fit the 160 KB LDS of a CU
+    ([13, 256, 256, 1] and [13, 512, 1] do, three 1024-wide layers do not)."""
 
     NAME = "NN"
     merge_mode = "mean"
@@ -493,8 +496,11 @@ class NN(Learner):
         self.st = torch.zeros(8, dtype=torch.float32, device=self.device)
         self._nact = torch.zeros(2, dtype=torch.float32, device=self.device)
         self._parity = 0
-        if self.device.type == "cuda" and D.mlp_lds_bytes(self.widths) > 160 * 1024:
-            raise ValueError("NN layer widths exceed the LDS budget of the fused kernel")
+        if self.device.type == "cuda" and not D.mlp_fits(self.widths):
+            raise ValueError(
+                f"NN layer widths {self.widths}: a 32-row mini-batch's activations and "
+                f"gradients ({D.mlp_stream_lds_bytes(self.widths)} bytes) exceed the "
+                f"{D.MLP_LDS_BUDGET}-byte LDS activation budget of a CU")
 
     def fit(self, batch, ctx):
         B = batch.B

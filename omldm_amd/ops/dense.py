@@ -401,6 +401,24 @@ def mlp_lds_bytes(widths: list[int]) -> int:
     return int(native.hip().omldm_mlp_lds_bytes(len(widths) - 1, _widths_arr(widths)))
 
 
+MLP_LDS_BUDGET = 160 * 1024   # LDS of one CU (gfx950)
+
+
+def mlp_stream_lds_bytes(widths: list[int]) -> int:
+    """LDS the streamed-weight form needs: the mini-batch's activations and gradients
+    (its weights stay in HBM)."""
+    return int(native.hip().omldm_mlp_stream_lds_bytes(len(widths) - 1, _widths_arr(widths)))
+
+
+def mlp_fits(widths: list[int]) -> bool:
+    """True when a GPU form takes the layer stack: the fused kernels (model in LDS) or the
+    streamed-weight form (activations in LDS)."""
+    if not 1 <= len(widths) - 1 <= MLP_MAX_LAYERS:
+        return False
+    fused, stream = mlp_lds_bytes(widths), mlp_stream_lds_bytes(widths)
+    return 0 < fused <= MLP_LDS_BUDGET or 0 < stream <= MLP_LDS_BUDGET
+
+
 def _mlp_unflatten(w: torch.Tensor, widths):
     out, o = [], 0
     for a, b in zip(widths[:-1], widths[1:]):
@@ -508,7 +526,8 @@ def mlp_round(w: torch.Tensor, x: torch.Tensor, y: torch.Tensor, R: int, S: int,
     if x.is_cuda:
         from omldm_amd.ops.linear import _workspace
 
-        # spoke deltas as plain rows + slab column sums (no per-spoke same-address atomics)
+        # spoke deltas as plain rows + slab column sums (no per-spoke same-address atomics);
+        # the streamed-weight form trains each spoke's working model in its row
         ws = _workspace(x.device, S * w.numel(), key="mlp_ws")
         check(native.hip().omldm_mlp_round(ptr(w), ptr(x), ptr(y), B, R, S, len(widths) - 1,
                                            _widths_arr(widths), task, act, lr, ptr(dacc),

@@ -116,6 +116,7 @@ HIP_SIGS = [
                                           i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, i32, vp]),
     ("omldm_multiclass_apply", i32, [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp]),
     ("omldm_mlp_lds_bytes", i64, [i32, vp]),
+    ("omldm_mlp_stream_lds_bytes", i64, [i32, vp]),
     ("omldm_mlp_round", i32, [vp, vp, vp, i64, i32, i32, i32, vp, i32, i32, f32, vp, vp, vp, vp,
                               vp]),
     ("omldm_mlp_forward", i32, [vp, vp, i64, i32, vp, i32, vp, vp]),
