@@ -23,15 +23,24 @@ namespace omldm {
 constexpr int kHtMaxC = 32;
 constexpr int kHtRegF = 8;  // features reduced per unrolled step of the wave aggregation
 
+// Float min / max through integer atomics, split on the sign BIT (not on v >= 0, which is
+// true for -0.0f, whose pattern is INT_MIN as a signed int: it overwrote every negative
+// minimum and never raised a maximum). Sign clear: among non-negative floats the signed int
+// order is the float order, and every negative float is a negative int — below for min, so
+// it stays; below for max, so it is replaced. Sign set: among negative floats the unsigned
+// order is the reverse float order and every non-negative float is a smaller unsigned — so
+// an unsigned max keeps the most negative (and -0.0f, the smallest of them, replaces only
+// non-negative values), an unsigned min keeps the value nearest zero and never replaces a
+// non-negative one (-0.0f raises any negative maximum, -inf included).
 __device__ __forceinline__ void atomic_min_f(float* a, float v) {
-  if (v >= 0.f)
+  if (__float_as_int(v) >= 0)
     atomicMin(reinterpret_cast<int*>(a), __float_as_int(v));
   else
     atomicMax(reinterpret_cast<unsigned int*>(a), __float_as_uint(v));
 }
 
 __device__ __forceinline__ void atomic_max_f(float* a, float v) {
-  if (v >= 0.f)
+  if (__float_as_int(v) >= 0)
     atomicMax(reinterpret_cast<int*>(a), __float_as_int(v));
   else
     atomicMin(reinterpret_cast<unsigned int*>(a), __float_as_uint(v));
@@ -674,13 +683,13 @@ __host__ __device__ inline HxLayout ht_exact_layout(int N, int d, int C, int nb,
 }
 
 __device__ __forceinline__ void lds_min_f(float* a, float v) {  // (range: sign-split ints)
-  if (v >= 0.f)
+  if (__float_as_int(v) >= 0)
     atomicMin(reinterpret_cast<int*>(a), __float_as_int(v));
   else
     atomicMax(reinterpret_cast<unsigned int*>(a), __float_as_uint(v));
 }
 __device__ __forceinline__ void lds_max_f(float* a, float v) {
-  if (v >= 0.f)
+  if (__float_as_int(v) >= 0)
     atomicMax(reinterpret_cast<int*>(a), __float_as_int(v));
   else
     atomicMin(reinterpret_cast<unsigned int*>(a), __float_as_uint(v));
@@ -846,7 +855,9 @@ __global__ __launch_bounds__(kHxNT) void ht_exact_kernel(
       if (valid && r >= base) {
         const float rem = ceilf(grace - since_l[leaf]);
         const int need = rem < 1.f ? 1 : (int)rem;
-        due = rank - consumed[leaf] + 1 == need;
+        // (only leaves are checked: a row that stops at an inner node of a tree deeper than
+        // depth + 1 levels counts there, as in ht_update, and the count is never reset)
+        due = tn[leaf].x < 0 && rank - consumed[leaf] + 1 == need;
       }
       if (tid == 0) s_first = 0x7fffffff;
       __syncthreads();
@@ -885,6 +896,20 @@ __global__ __launch_bounds__(kHxNT) void ht_exact_kernel(
               if (f < d) put(f, v[f]);
           } else {
             for (int f = 0; f < d; ++f) put(f, xr[f]);
+          }
+        } else {
+          // the row stopped at an inner node (routing ends after depth + 1 steps): its
+          // statistics go to the node's global rows, as ht_update adds them; no leaf slot
+          // shadows those rows, and the launch never reads them
+          atomicAdd(&T.cc[(size_t)leaf * C + yi], 1.f);
+          for (int f = 0; f < d; ++f) {
+            const size_t o = ((size_t)leaf * d + f) * C + yi;
+            const float v = xr[f];
+            atomicAdd(&T.S0[o], 1.f);
+            atomicAdd(&T.S1[o], v);
+            atomicAdd(&T.S2[o], v * v);
+            atomic_min_f(&T.lo[(size_t)leaf * d + f], v);
+            atomic_max_f(&T.hi[(size_t)leaf * d + f], v);
           }
         }
         atomicAdd(&since_l[leaf], 1.f);

@@ -825,7 +825,7 @@ class HT(Learner):
                 (nl + nr).clamp(min=1e-12)
             gain = torch.where(span.unsqueeze(1) > 0, gain, torch.full_like(gain, -1))
             per_feat, arg = gain.max(1)
-            order = torch.argsort(per_feat, descending=True)
+            order = torch.argsort(per_feat, descending=True, stable=True)  # ties: lowest index
             g1 = float(per_feat[order[0]])
             g2 = float(per_feat[order[1]]) if self.d > 1 else 0.0
             R = math.log2(self.Cn)

@@ -5,14 +5,12 @@ omldm/operators/spoke/FlinkSpoke.scala:92-107): every training point updates its
 statistics, and a leaf re-evaluates its split as soon as ``gracePeriod`` points reached it
 since its last check — so a split made mid-stream routes the very next point. The engine
 (models/dense.py: HT, csrc/kernels/hoeffding.hip) updates the statistics of ``checkEvery``
-rows at a time (default 1,024) and then checks every due leaf. The NumPy oracle below is
-the per-point algorithm with the SAME split criterion (Gaussian class-conditional
-statistics, nBins candidate thresholds, information gain, Hoeffding bound with tie
+rows at a time (default 1,024) and then checks every due leaf. The NumPy oracle
+(tests/ht_ref.py: VFDT) is the per-point algorithm with the SAME split criterion (Gaussian
+class-conditional statistics, nBins candidate thresholds, information gain, Hoeffding bound with tie
 threshold τ); the test pins the quality gap at the engine's 65,536-row ticks on a stream
 that needs several levels (checking only at tick ends: 0.93 → 0.56 accuracy).
 """
-import math
-
 import numpy as np
 import pytest
 import torch
@@ -20,95 +18,7 @@ import torch
 from omldm_amd.api.batch import FeatureSpace, HashedBatch
 from omldm_amd.models.base import RoundContext
 from omldm_amd.models.dense import HT
-
-
-def _entropy(c):
-    t = c.sum(-1, keepdims=True)
-    t = np.maximum(t, 1e-12)
-    p = c / t
-    return -(p * np.log2(np.maximum(p, 1e-12))).sum(-1)
-
-
-class VFDT:
-    """Per-point Hoeffding tree with models/dense.py:HT's split criterion."""
-
-    def __init__(self, d, C, grace=200, delta=1e-7, tau=0.05, nb=16, max_nodes=255, depth=12):
-        self.d, self.C, self.grace, self.delta, self.tau, self.nb = d, C, grace, delta, tau, nb
-        self.N, self.depth = max_nodes, depth
-        N = max_nodes
-        self.feat = -np.ones(N, dtype=np.int64)
-        self.thr = np.zeros(N)
-        self.left = np.zeros(N, dtype=np.int64)
-        self.right = np.zeros(N, dtype=np.int64)
-        self.cc = np.zeros((N, C))
-        self.S0 = np.zeros((N, d, C))
-        self.S1 = np.zeros((N, d, C))
-        self.S2 = np.zeros((N, d, C))
-        self.lo = np.full((N, d), np.inf)
-        self.hi = np.full((N, d), -np.inf)
-        self.since = np.zeros(N)
-        self.nnodes = 1
-
-    def leaf(self, x):
-        node = 0
-        for _ in range(self.depth + 1):
-            f = self.feat[node]
-            if f < 0:
-                break
-            node = self.left[node] if x[f] <= self.thr[node] else self.right[node]
-        return node
-
-    def learn(self, x, y):
-        n = self.leaf(x)
-        c = int(min(max(y, 0), self.C - 1))
-        self.cc[n, c] += 1
-        self.S0[n, :, c] += 1
-        self.S1[n, :, c] += x
-        self.S2[n, :, c] += x * x
-        self.lo[n] = np.minimum(self.lo[n], x)
-        self.hi[n] = np.maximum(self.hi[n], x)
-        self.since[n] += 1
-        if self.since[n] >= self.grace:
-            self._try_split(n)
-
-    def _try_split(self, node):
-        self.since[node] = 0
-        cc = self.cc[node]
-        n_total = cc.sum()
-        if n_total < 2 or self.nnodes + 2 > self.N or (cc > 0).sum() < 2:
-            return
-        S0, S1, S2 = self.S0[node], self.S1[node], self.S2[node]
-        mu = S1 / np.maximum(S0, 1)
-        var = np.maximum(S2 / np.maximum(S0, 1) - mu * mu, 1e-6)
-        sd = np.sqrt(var)
-        lo, hi = self.lo[node], self.hi[node]
-        span = np.maximum(hi - lo, 0)
-        q = np.linspace(0, 1, self.nb + 2)[1:-1]
-        t = lo[:, None] + span[:, None] * q[None, :]
-        z = (t[:, :, None] - mu[:, None, :]) / sd[:, None, :]
-        cdf = 0.5 * (1 + np.vectorize(math.erf)(z / math.sqrt(2)))
-        left = S0[:, None, :] * cdf
-        right = S0[:, None, :] - left
-        nl, nr = left.sum(-1), right.sum(-1)
-        gain = _entropy(cc) - (nl * _entropy(left) + nr * _entropy(right)) / np.maximum(nl + nr, 1e-12)
-        gain = np.where(span[:, None] > 0, gain, -1.0)
-        per, arg = gain.max(1), gain.argmax(1)
-        order = np.argsort(-per, kind="stable")
-        g1 = per[order[0]]
-        g2 = per[order[1]] if self.d > 1 else 0.0
-        R = math.log2(self.C)
-        eps = math.sqrt(R * R * math.log(1.0 / self.delta) / (2.0 * n_total))
-        if g1 > 0 and (g1 - g2 > eps or eps < self.tau):
-            f = int(order[0])
-            a, b = self.nnodes, self.nnodes + 1
-            self.nnodes += 2
-            self.feat[node], self.thr[node] = f, t[f, arg[f]]
-            self.left[node], self.right[node] = a, b
-            self.cc[a] = left[f, arg[f]]
-            self.cc[b] = right[f, arg[f]]
-
-    def predict(self, X):
-        return np.array([self.cc[self.leaf(x)].argmax() for x in X])
+from tests.ht_ref import VFDT
 
 
 def _stream(B, seed):
