@@ -8,8 +8,9 @@
 // of the chunk; step s broadcasts point s with v_readlane (scalar registers), every lane
 // computes its centroid's squared distance, a DPP/readlane argmin picks j*, and lane j*
 // moves its centroid — no LDS, no barrier, no memory access on the per-point chain.
-// Seeding: while fewer than k centroids exist (n_j = 0), a point becomes the next
-// centroid (n = 1). Rows with a NaN target are not training points and are skipped.
+// Seeding: while fewer than k centroids exist (the leading run of n_j > 0 is shorter than
+// k), a point becomes the next centroid (n = 1). Rows with a NaN target are not training
+// points and are skipped (their features may hold anything); training rows are finite.
 #include "common.h"
 
 #include <algorithm>
@@ -43,6 +44,14 @@ __device__ __forceinline__ int wave_argmin(float v, float& vmin) {
   return at ? __builtin_ctzll(at) : 0;  // (no lane: every distance NaN)
 }
 
+// The seeded centroids on entry: the leading run of positive counts (the CPU oracle's rule:
+// seeding resumes at the first centroid without a count, whatever lies behind it). `has`:
+// this lane's centroid has a count; lanes past the model pass false.
+__device__ __forceinline__ int seeded_prefix(bool has) {
+  const unsigned long long b = __builtin_amdgcn_ballot_w64(has);
+  return ~b ? __builtin_ctzll(~b) : 64;
+}
+
 template <int DM>
 __global__ __launch_bounds__(64) void kmeans_seq_kernel(const float* __restrict__ x, int ldx,
                                                         const float* __restrict__ y, int B,
@@ -55,8 +64,7 @@ __global__ __launch_bounds__(64) void kmeans_seq_kernel(const float* __restrict_
 #pragma unroll
   for (int i = 0; i < DM; ++i) c[i] = (mine && i < d) ? cent[(size_t)lane * d + i] : 0.f;
   float n = mine ? cnt[lane] : 0.f;
-  // seeded centroids: a prefix (seeding fills them in order)
-  int seeded = __popcll(__builtin_amdgcn_ballot_w64(mine && n > 0.f));
+  int seeded = seeded_prefix(mine && n > 0.f);
   double inertia = 0.0, fitted = 0.0;
   float xr[DM];
   float yr;
@@ -152,9 +160,9 @@ __global__ __launch_bounds__(NW * 64) void kmeans_seq_wg_kernel(const float* __r
   const bool mine = tid < k;
   for (int i = tid; i < k * d; i += NW * 64) C[(i / d) * ds + i % d] = cent[i];
   float n = mine ? cnt[tid] : 0.f;
-  if (tid == 0) *sseed = 0;
+  if (tid == 0) *sseed = k;
   __syncthreads();
-  if (mine && n > 0.f) atomicAdd(sseed, 1);  // seeded centroids form a prefix
+  if (mine && !(n > 0.f)) atomicMin(sseed, tid);  // the first centroid without a count
   __syncthreads();
   int seeded = *sseed;
   double inertia = 0.0, fitted = 0.0;
@@ -240,8 +248,9 @@ __global__ __launch_bounds__(NW * 64) void kmeans_seq_wg_kernel(const float* __r
 //    order is the value order) in fused DPP steps, then one ballot of the lanes equal to
 //    the minimum: its lowest lane's centroid wins, the same lowest-index tie rule as the
 //    oracle (all G lanes of a centroid hold the bitwise same sum: the DPP adds commute);
-//  * the winning centroid's lanes move it: r = 1/n (v_rcp + one Newton step: the correctly
-//    rounded reciprocal the oracle's 1.f/n gives), c ← fma(r, x − c, c).
+//  * the winning centroid's lanes move it: r = 1/n (v_rcp + one Newton step: bitwise the
+//    oracle's 1.f/n on gfx950 for every count of the sweep in tests/test_kmeans_seq.py,
+//    n ≤ 4096, 2^p and 2^p ± 1 up to 2^24, half-integers), c ← fma(r, x − c, c).
 // (the DPP moves' "old" operand is the operation's identity, so lanes with no source lane —
 // or in rows the row mask leaves out — fold to a no-op and the move fuses into the VALU op)
 template <int CTRL, int RM>
@@ -364,8 +373,8 @@ __global__ __launch_bounds__(64) void kmeans_fast_kernel(const float* __restrict
 #pragma unroll
   for (int i = 0; i < DPL; ++i) c[i] = (mine && c0 + i < d) ? cent[(size_t)grp * d + c0 + i] : 0.f;
   float n = mine ? cnt[grp] : 0.f;
-  // seeded centroids form a prefix (seeding fills them in order)
-  int seeded = __popcll(__builtin_amdgcn_ballot_w64(part == 0 && mine && n > 0.f));
+  // (a group's first lane speaks for it, the others pass true: the first gap is lane G·seeded)
+  int seeded = seeded_prefix(part != 0 || (mine && n > 0.f)) / G;
   const unsigned pad = mine ? 0u : 0x7f800000u;  // OR-ed into a key: never the minimum
   double inertia = 0.0, fitted = 0.0;
   const int nchunks = (B + 63) / 64;
@@ -461,7 +470,7 @@ __global__ __launch_bounds__(256) void kmeans_mw_kernel(const float* __restrict_
   float c[CPL][DPL];
   float n[CPL];
   unsigned pad[CPL];
-  if (tid == 0) s_seed = 0;
+  if (tid == 0) s_seed = k;
   __syncthreads();
 #pragma unroll
   for (int q = 0; q < CPL; ++q) {
@@ -471,7 +480,7 @@ __global__ __launch_bounds__(256) void kmeans_mw_kernel(const float* __restrict_
     for (int i = 0; i < DPL; ++i) c[q][i] = (mine && i < d) ? cent[(size_t)j * d + i] : 0.f;
     n[q] = mine ? cnt[j] : 0.f;
     pad[q] = mine ? 0u : 0x7f800000u;
-    if (mine && n[q] > 0.f) atomicMax(&s_seed, j + 1);  // seeded centroids form a prefix
+    if (mine && !(n[q] > 0.f)) atomicMin(&s_seed, j);  // the first centroid without a count
   }
   __syncthreads();
   int seeded = s_seed;
@@ -584,7 +593,8 @@ __global__ __launch_bounds__(256) void kmeans_mw_kernel(const float* __restrict_
 // coordinates are staged in LDS, thread t scans centroids t, t + 1024, … keeping its lowest
 // (distance, index), the block minimum goes through LDS (ties: lowest index), then every
 // thread moves a slice of the winner's coordinates — the same per-point order and update
-// as the CPU oracle, at any (k, d). Counts stay in LDS up to 32768 centroids, else in HBM.
+// as the CPU oracle, at any (k, d). The counts stay in HBM with the centroids (thread 0
+// moves the winner's count).
 constexpr int kBigNT = 1024;
 constexpr int kBigDMax = 8192;  // staged coordinates per point (32 KiB)
 
@@ -596,10 +606,10 @@ __global__ __launch_bounds__(kBigNT) void kmeans_seq_big_kernel(
   __shared__ int s_seed, s_win;
   __shared__ float s_r;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) s_seed = 0;
+  if (tid == 0) s_seed = k;
   __syncthreads();
   for (int j = tid; j < k; j += kBigNT)
-    if (cnt[j] > 0.f) atomicMax(&s_seed, j + 1);  // seeded centroids form a prefix
+    if (!(cnt[j] > 0.f)) atomicMin(&s_seed, j);  // the first centroid without a count
   __syncthreads();
   int seeded = s_seed;
   double inertia = 0.0, fitted = 0.0;
@@ -700,42 +710,22 @@ static bool kmeans_fast_geometry(int d, int k, int& G, int& DPL, int& CPL, int& 
   return G * DPL <= 64;
 }
 
-template <int G, int DPL, int ND>
-static bool launch_one(int g, int dpl, int cpl, int nd, hipStream_t st, const float* x, int ldx,
-                       const float* y, int B, int d, int k, float* cent, float* cnt, double* cum) {
-  if (cpl != 0 || g != G || dpl != DPL || nd != ND) return false;
-  hipLaunchKernelGGL((kmeans_fast_kernel<G, DPL, ND>), dim3(1), dim3(64), 0, st, x, ldx, y, B, d,
-                     k, cent, cnt, cum);
-  return true;
+static bool kmeans_wg_fits(int d, int k) {
+  const int nw = (k + 63) / 64;
+  return d >= 1 && d <= 256 && k >= 1 && k <= 1024 &&
+         kmeans_wg_lds(d, k, nw <= 4 ? 4 : 16) <= 160 * 1024;
 }
 
-template <int CPL, int DPL, int ND>
-static bool launch_mw(int cpl, int dpl, int nd, hipStream_t st, const float* x, int ldx,
-                      const float* y, int B, int d, int k, float* cent, float* cnt, double* cum) {
-  if (cpl != CPL || dpl != DPL || nd != ND) return false;
-  hipLaunchKernelGGL((kmeans_mw_kernel<CPL, DPL, ND>), dim3(1), dim3(256), 0, st, x, ldx, y, B,
-                     d, k, cent, cnt, cum);
-  return true;
-}
-
-static bool kmeans_fast(hipStream_t st, const float* x, int ldx, const float* y, int B, int d,
-                        int k, float* cent, float* cnt, double* cum) {
-  int g, dpl, cpl, nd;
-  if (!kmeans_fast_geometry(d, k, g, dpl, cpl, nd)) return false;
-#define K1(G, DPL, ND) launch_one<G, DPL, ND>(g, dpl, cpl, nd, st, x, ldx, y, B, d, k, cent, cnt, cum)
-#define KM(CPL, DPL, ND) launch_mw<CPL, DPL, ND>(cpl, dpl, nd, st, x, ldx, y, B, d, k, cent, cnt, cum)
-  return K1(16, 4, 4) || K1(8, 4, 4) || K1(8, 8, 8) || K1(4, 4, 4) || K1(4, 8, 8) ||
-         K1(4, 16, 16) || K1(2, 4, 4) || K1(2, 8, 8) || K1(2, 16, 16) || K1(2, 32, 32) ||
-         K1(1, 4, 4) || K1(1, 8, 8) || K1(1, 8, 6) || K1(1, 16, 16) ||
-         K1(1, 16, 14) || K1(1, 32, 32) || K1(1, 32, 30) || K1(1, 64, 64) || K1(1, 64, 62) ||
-         KM(1, 4, 4) || KM(1, 8, 8) || KM(1, 8, 6) || KM(1, 16, 16) || KM(1, 16, 14) ||
-         KM(1, 32, 32) || KM(1, 32, 30) || KM(1, 64, 64) || KM(1, 64, 62) || KM(2, 4, 4) ||
-         KM(2, 8, 8) || KM(2, 8, 6) || KM(2, 16, 16) || KM(2, 16, 14) || KM(2, 32, 32) ||
-         KM(2, 32, 30) || KM(2, 64, 64) || KM(2, 64, 62) || KM(4, 4, 4) || KM(4, 8, 8) ||
-         KM(4, 8, 6) || KM(4, 16, 16) || KM(4, 16, 14) || KM(4, 32, 32) || KM(4, 32, 30);
-#undef K1
-#undef KM
-}
+// Every instantiation of the fast forms, once: the plan query and the launcher both expand
+// this list. K1(G, DPL, ND): kmeans_fast_kernel; KM(CPL, DPL, ND): kmeans_mw_kernel.
+#define KMEANS_FAST_LIST(K1, KM)                                                                \
+  K1(16, 4, 4) K1(8, 4, 4) K1(8, 8, 8) K1(4, 4, 4) K1(4, 8, 8) K1(4, 16, 16) K1(2, 4, 4)        \
+  K1(2, 8, 8) K1(2, 16, 16) K1(2, 32, 32) K1(1, 4, 4) K1(1, 8, 8) K1(1, 8, 6) K1(1, 16, 16)     \
+  K1(1, 16, 14) K1(1, 32, 32) K1(1, 32, 30) K1(1, 64, 64) K1(1, 64, 62)                         \
+  KM(1, 4, 4) KM(1, 8, 8) KM(1, 8, 6) KM(1, 16, 16) KM(1, 16, 14) KM(1, 32, 32) KM(1, 32, 30)   \
+  KM(1, 64, 64) KM(1, 64, 62) KM(2, 4, 4) KM(2, 8, 8) KM(2, 8, 6) KM(2, 16, 16) KM(2, 16, 14)   \
+  KM(2, 32, 32) KM(2, 32, 30) KM(2, 64, 64) KM(2, 64, 62) KM(4, 4, 4) KM(4, 8, 8) KM(4, 8, 6)   \
+  KM(4, 16, 16) KM(4, 16, 14) KM(4, 32, 32) KM(4, 32, 30)
 
 static int g_kmeans_form = -1;  // -1 unset; 0 the earlier forms; 1 the fast one-wave form
 
@@ -750,57 +740,107 @@ OMLDM_API int omldm_kmeans_seq_form(int form) {
   return g_kmeans_form;
 }
 
-static bool kmeans_wg_fits(int d, int k) {
-  const int nw = (k + 63) / 64;
-  return d >= 1 && d <= 256 && k >= 1 && k <= 1024 &&
-         kmeans_wg_lds(d, k, nw <= 4 ? 4 : 16) <= 160 * 1024;
-}
-
 // Every (d, k) with d ≤ 8192 runs exactly: the register / LDS forms where they fit, the
 // HBM-resident form past them.
 OMLDM_API int omldm_kmeans_seq_fits(int d, int k) {
   return d >= 1 && k >= 1 && d <= kBigDMax;
 }
 
+// The kernels a plan names (out[0]) and their template parameters (out[1..3]).
+enum {
+  kKmSeq = 0,   // kmeans_seq_kernel<DM>:           out[1] = DM
+  kKmWg = 1,    // kmeans_seq_wg_kernel<NW>:        out[1] = NW
+  kKmFast = 2,  // kmeans_fast_kernel<G, DPL, ND>:  out[1..3] = G, DPL, ND
+  kKmMw = 3,    // kmeans_mw_kernel<CPL, DPL, ND>:  out[1..3] = CPL, DPL, ND
+  kKmBig = 4,   // kmeans_seq_big_kernel
+};
+
+// The routing of omldm_kmeans_seq (host code only; the launcher below consumes it): which
+// kernel runs (d, k) under `form` (< 0: the form in use), with which template parameters.
+// 0: out is filled; −1: (d, k) is refused; −2: the fast geometry holds but no instantiation
+// of it was compiled (the launcher then fails: there is no fall-back to a slower form).
+OMLDM_API int omldm_kmeans_seq_plan(int d, int k, int form, int* out) {
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (!omldm_kmeans_seq_fits(d, k)) return -1;
+  if (form < 0) form = omldm_kmeans_seq_form(-1);
+  int g, dpl, cpl, nd;
+  if (form && kmeans_fast_geometry(d, k, g, dpl, cpl, nd)) {
+    out[0] = cpl ? kKmMw : kKmFast;
+    out[1] = cpl ? cpl : g;
+    out[2] = dpl;
+    out[3] = nd;
+#define K1(G, DPL, ND) || (!cpl && g == G && dpl == DPL && nd == ND)
+#define KM(CPL, DPL, ND) || (cpl == CPL && dpl == DPL && nd == ND)
+    const bool have = false KMEANS_FAST_LIST(K1, KM);
+#undef K1
+#undef KM
+    return have ? 0 : -2;
+  }
+  if (kmeans_one_wave(d, k)) {
+    out[0] = kKmSeq;
+    out[1] = d <= 16 ? 16 : d <= 32 ? 32 : 64;
+  } else if (kmeans_wg_fits(d, k)) {
+    out[0] = kKmWg;
+    out[1] = (k + 63) / 64 <= 4 ? 4 : 16;
+  } else {
+    out[0] = kKmBig;  // past the LDS: centroids in HBM
+  }
+  return 0;
+}
+
 // x [B, ldx] fp32 (first d columns used), y [B] (NaN: not a training point; nullptr: all
 // train), cent [k, d], cnt [k], cum (cum[0] += Σ squared distance to the chosen
-// centroid, cum[1] += points fitted) — all device pointers; one wave, one launch.
+// centroid, cum[1] += points fitted) — all device pointers; one workgroup, one launch.
 OMLDM_API int omldm_kmeans_seq(const float* x, int ldx, const float* y, int B, int d, int k,
                                float* cent, float* cnt, double* cum, void* stream) {
-  if (!omldm_kmeans_seq_fits(d, k) || ldx < d) return -1;
+  int p[4];
+  if (omldm_kmeans_seq_plan(d, k, -1, p) || ldx < d) return -1;
   if (B <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (omldm_kmeans_seq_form(-1) && kmeans_fast(st, x, ldx, y, B, d, k, cent, cnt, cum))
-    return (int)hipGetLastError();
-  if (!kmeans_one_wave(d, k) && !kmeans_wg_fits(d, k)) {  // past the LDS: centroids in HBM
-    hipLaunchKernelGGL(kmeans_seq_big_kernel, dim3(1), dim3(kBigNT), 0, st, x, ldx, y, B, d, k,
-                       cent, cnt, cum);
-    return (int)hipGetLastError();
-  }
-  if (!kmeans_one_wave(d, k)) {  // the workgroup form
-    const int nw = (k + 63) / 64 <= 4 ? 4 : 16;
-    const size_t lds = kmeans_wg_lds(d, k, nw);
-    if (nw == 4) {
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&kmeans_seq_wg_kernel<4>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL(kmeans_seq_wg_kernel<4>, dim3(1), dim3(256), lds, st, x, ldx, y, B, d,
-                         k, cent, cnt, cum);
-    } else {
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&kmeans_seq_wg_kernel<16>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL(kmeans_seq_wg_kernel<16>, dim3(1), dim3(1024), lds, st, x, ldx, y, B,
-                         d, k, cent, cnt, cum);
+#define KM_ARGS x, ldx, y, B, d, k, cent, cnt, cum
+  switch (p[0]) {
+    case kKmFast:
+#define K1(G, DPL, ND)                                                                          \
+  if (p[1] == G && p[2] == DPL && p[3] == ND)                                                   \
+    hipLaunchKernelGGL((kmeans_fast_kernel<G, DPL, ND>), dim3(1), dim3(64), 0, st, KM_ARGS);
+#define KM(CPL, DPL, ND)
+      KMEANS_FAST_LIST(K1, KM)
+#undef K1
+#undef KM
+      break;
+    case kKmMw:
+#define K1(G, DPL, ND)
+#define KM(CPL, DPL, ND)                                                                        \
+  if (p[1] == CPL && p[2] == DPL && p[3] == ND)                                                 \
+    hipLaunchKernelGGL((kmeans_mw_kernel<CPL, DPL, ND>), dim3(1), dim3(256), 0, st, KM_ARGS);
+      KMEANS_FAST_LIST(K1, KM)
+#undef K1
+#undef KM
+      break;
+    case kKmBig:
+      hipLaunchKernelGGL(kmeans_seq_big_kernel, dim3(1), dim3(kBigNT), 0, st, KM_ARGS);
+      break;
+    case kKmWg: {
+      const size_t lds = kmeans_wg_lds(d, k, p[1]);
+      if (p[1] == 4) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&kmeans_seq_wg_kernel<4>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipLaunchKernelGGL(kmeans_seq_wg_kernel<4>, dim3(1), dim3(256), lds, st, KM_ARGS);
+      } else {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&kmeans_seq_wg_kernel<16>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipLaunchKernelGGL(kmeans_seq_wg_kernel<16>, dim3(1), dim3(1024), lds, st, KM_ARGS);
+      }
+      break;
     }
-    return (int)hipGetLastError();
+    default:
+      if (p[1] == 16)
+        hipLaunchKernelGGL(kmeans_seq_kernel<16>, dim3(1), dim3(64), 0, st, KM_ARGS);
+      else if (p[1] == 32)
+        hipLaunchKernelGGL(kmeans_seq_kernel<32>, dim3(1), dim3(64), 0, st, KM_ARGS);
+      else
+        hipLaunchKernelGGL(kmeans_seq_kernel<64>, dim3(1), dim3(64), 0, st, KM_ARGS);
   }
-  if (d <= 16)
-    hipLaunchKernelGGL(kmeans_seq_kernel<16>, dim3(1), dim3(64), 0, st, x, ldx, y, B, d, k, cent,
-                       cnt, cum);
-  else if (d <= 32)
-    hipLaunchKernelGGL(kmeans_seq_kernel<32>, dim3(1), dim3(64), 0, st, x, ldx, y, B, d, k, cent,
-                       cnt, cum);
-  else
-    hipLaunchKernelGGL(kmeans_seq_kernel<64>, dim3(1), dim3(64), 0, st, x, ldx, y, B, d, k, cent,
-                       cnt, cum);
+#undef KM_ARGS
   return (int)hipGetLastError();
 }

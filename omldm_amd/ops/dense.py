@@ -368,6 +368,27 @@ def kmeans_seq_form(form: int = -1) -> int:
     return int(native.hip().omldm_kmeans_seq_form(int(form)))
 
 
+KMEANS_SEQ_KERNELS = ("seq", "wg", "fast", "mw", "big")  # csrc/kernels/kmeans_seq.hip kKm*
+
+
+def kmeans_seq_plan(d: int, k: int, form: int = -1) -> tuple | None:
+    """The kernel the launcher picks for (d, k) under ``form`` (< 0: the form in use), from
+    the launcher's own routing (host code, no launch): ``("seq", DM)``, ``("wg", NW)``,
+    ``("fast", G, DPL, ND)``, ``("mw", CPL, DPL, ND)`` or ``("big",)``; None where (d, k) is
+    refused. Raises if the fast geometry holds and no instantiation of it was compiled."""
+    import ctypes
+
+    out = (ctypes.c_int * 4)()
+    rc = int(native.hip().omldm_kmeans_seq_plan(int(d), int(k), int(form), out))
+    if rc == -1:
+        return None
+    if rc:
+        raise RuntimeError(f"kmeans_seq: no instantiation for geometry {tuple(out)} at "
+                           f"d={d}, k={k}")
+    name = KMEANS_SEQ_KERNELS[out[0]]
+    return (name, *out[1:{"seq": 2, "wg": 2, "big": 1}.get(name, 4)])
+
+
 def kmeans_seq_fits(d: int, k: int) -> bool:
     """The exact sequential kernels take every (d, k) with d ≤ 8192
     (csrc/kernels/kmeans_seq.hip): one wave for k ≤ 64 (G lanes per centroid), four waves

@@ -143,6 +143,7 @@ HIP_SIGS = [
     ("omldm_scan3mc_debug", i32, [vp]),
     ("omldm_mlp_form", i32, [i32]),
     ("omldm_kmeans_seq_form", i32, [i32]),
+    ("omldm_kmeans_seq_plan", i32, [i32, i32, i32, vp]),
     ("omldm_kmeans_seq", i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]),
     ("omldm_ipc_alloc", vp, [i64]),
     ("omldm_ipc_free", i32, [vp]),

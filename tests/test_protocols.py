@@ -7,6 +7,7 @@ Invariants checked per protocol:
 * EASGD: centre variables identical; GM / FGM: estimates identical, syncs counted;
 * SingleLearner: only the hub trains, replicas equal to the hub model.
 """
+import gc
 import os
 import socket
 import tempfile
@@ -31,6 +32,14 @@ def _free_port():
     p = s.getsockname()[1]
     s.close()
     return p
+
+
+def _fork(fn, args, nprocs):
+    """Fork the workers with no garbage pending: in a whole-suite run this process holds a
+    GPU context from earlier tests, and a collection inside a forked child would finalise
+    their leftover device objects there (a child must not touch the parent's context)."""
+    gc.collect()
+    mp.start_processes(fn, args=args, nprocs=nprocs, start_method="fork")
 
 
 def _worker(rank, world, port, out, learner, proto, cfg, rounds, B, task):
@@ -59,8 +68,7 @@ def _worker(rank, world, port, out, learner, proto, cfg, rounds, B, task):
 
 def run(world, learner, proto, cfg=None, rounds=4, B=256, task=0):
     with tempfile.TemporaryDirectory() as d:
-        mp.start_processes(_worker, args=(world, _free_port(), d, learner, proto, cfg or {},
-                                          rounds, B, task), nprocs=world, start_method="fork")
+        _fork(_worker, (world, _free_port(), d, learner, proto, cfg or {}, rounds, B, task), world)
         return [torch.load(os.path.join(d, f"r{r}.pt"), weights_only=True) for r in range(world)]
 
 
@@ -180,8 +188,7 @@ def test_coalesced_buckets_world2():
     """bucketBytes caps a coalesced collective; small caps split (and slice) buffers,
     results equal plain per-tensor all-reduces."""
     with tempfile.TemporaryDirectory() as d:
-        mp.start_processes(_bucket_worker, args=(2, _free_port(), d), nprocs=2,
-                           start_method="fork")
+        _fork(_bucket_worker, (2, _free_port(), d), 2)
         res = [torch.load(os.path.join(d, f"r{r}.pt"), weights_only=True) for r in range(2)]
     assert all(r["ok"] for r in res)
     assert res[0]["collectives"] > 3  # the 64-byte cap produced many buckets
@@ -235,8 +242,7 @@ def _ckpt_worker(rank, world, port, out, learner, proto, cfg, rounds, split, B, 
 
 def _run_ckpt(proto, cfg, split, learner="ORR", rounds=8, task=1):
     with tempfile.TemporaryDirectory() as d:
-        mp.start_processes(_ckpt_worker, args=(2, _free_port(), d, learner, proto, cfg, rounds,
-                                               split, 128, task), nprocs=2, start_method="fork")
+        _fork(_ckpt_worker, (2, _free_port(), d, learner, proto, cfg, rounds, split, 128, task), 2)
         return [torch.load(os.path.join(d, f"r{r}.pt"), weights_only=True) for r in range(2)]
 
 
