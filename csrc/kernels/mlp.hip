@@ -1,40 +1,54 @@
-// NN learner: fused MLP training and inference on the fp32 matrix cores.
+// NN learner: MLP training and inference on the matrix cores.
 //
 // Reference: the NN learner runs DL4J MultiLayerNetwork.fit on ND4J/OpenBLAS — GEMM,
 // the row-wise bias broadcast that crashed (BaseLayer.preOutputWithPreNorm → doRowWise →
 // execBroadcast, hs_err_pid77107.log:97-110), activations and an SGD step, each a
 // separate native call per layer per mini-batch.
 //
-// Design (one kernel per protocol round):
-// * one workgroup (4 waves) = one virtual spoke. It copies the round-start model into
-//   LDS and runs plain mini-batch SGD over its row range: forward, loss gradient,
-//   backward and the weight update never leave LDS/registers;
-// * every GEMM-shaped step is v_mfma_f32_32x32x2_f32 on 32-row mini-batches:
-//     forward   H_{l+1} = act(H_l · W_lᵀ + b_l)     (bias + activation fused in the
-//                                                     epilogue: ReLU / tanh / sigmoid / identity)
-//     backward  dH_l    = (dZ_{l+1} · W_l) ⊙ act'(H_l)  (derivative from the stored output)
-//               W_l    -= η · dZ_{l+1}ᵀ · H_l       (applied straight from the MFMA
-//                                                     accumulators — each element has
-//                                                     exactly one owner lane)
-//   widths are zero-padded to 32; padding stays exactly zero through every step;
-// * LDS row strides are padded to an odd number of floats so the 32 lanes of an MFMA
-//   operand column hit distinct banks;
-// * round end: each spoke adds its model delta to a device accumulator and an apply
-//   pass averages the deltas of the active spokes (omldm_multiclass_apply) — the
-//   intra-GPU hub; across GPUs the protocol ships the flat parameter vector over RCCL.
+// Map of the file. One protocol round is one launch of a round kernel (+ the column sums),
+// inference one launch of a forward kernel; omldm_mlp_plan picks both for a layer stack:
+// * fused-32 (v1): mlp_round_kernel, 4 waves, and mlp_forward_kernel. The model sits in
+//   LDS with widths zero-padded to 32; the loss is a serial pass per row, so any output
+//   width goes. Takes the stacks whose 32-padded layout fits one CU's LDS and that
+//   fused-16 does not take; its forward kernel serves every stack with that layout,
+//   whichever kernel trains it.
+// * fused-16 (v2, the default where it applies): mlp_round2_kernel, 16 waves. Widths
+//   padded to 16, the loss fused into the last layer's epilogue, one barrier per
+//   backward layer. Takes output widths ≤ 16 whose 16-padded layout (one more gradient
+//   buffer and the bias gradients) fits.
+// * streamed: mlp_round_stream_kernel, 16 waves, and mlp_forward_stream_kernel, 8 waves.
+//   Only the mini-batch is in LDS, the weights stream from HBM. Takes what no fused layout
+//   holds, up to kMlpLdsMax of activations, and everything under form 4.
+// What the forms share:
+// * the mini-batch: one workgroup = one virtual spoke running plain SGD over its row range
+//   in steps of kMB = 32 rows (rows with a NaN label are left out, a step without labels
+//   is skipped), every GEMM-shaped step on 16×16 MFMA tiles (gemm16p; the streamed forward
+//   and dH read their weight operand from HBM instead):
+//     forward   H_{l+1} = act(H_l · W_lᵀ + b_l)
+//     backward  dH_l    = (dZ_{l+1} · W_l) ⊙ act'(H_l)   (derivative from the stored output)
+//               W_l    -= η · dZ_{l+1}ᵀ · H_l             (from the accumulators: one owner
+//                                                          lane per weight)
+//   padded columns stay exactly zero through every step;
+// * the flat layout of the parameter vector: per layer W_l [n_{l+1} × n_l] row-major, then
+//   b_l (woff / boff) — what the protocol ships and the hub averages;
+// * the delta hand-off: at round end a spoke writes Δ = W_spoke − W_0 into its row of the
+//   S × nparams workspace, mlp_colsum_kernel folds the rows into dacc, and an apply pass
+//   averages over the active spokes (omldm_multiclass_apply).
+// LDS row strides are ≡ 4 floats mod 64 banks, so the 16-lane groups of a b128 operand read
+// hit disjoint banks.
 #include "common.h"
 
 namespace omldm {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kMB = 32;
+constexpr int kT = 16;  // output tile of every GEMM: 16×16
 constexpr int kMaxLayers = 4;
 
 enum MlpAct : int { kRelu = 0, kTanh = 1, kSigmoid = 2, kIdentity = 3 };
 
 struct MlpDesc {
   int L, task, K, act;  // act: hidden-layer activation (MlpAct)
-  int bf16;             // 1: GEMM operands rounded to bf16 (v_mfma_f32_32x32x16_bf16)
+  int bf16;             // 1: GEMM operands rounded to bf16 (v_mfma_f32_16x16x16_bf16)
   int n[kMaxLayers + 1], np[kMaxLayers + 1];
   int woff[kMaxLayers], boff[kMaxLayers];
   int lw[kMaxLayers], lb[kMaxLayers], ldw[kMaxLayers];
@@ -45,113 +59,30 @@ struct MlpDesc {
   int lbg[kMaxLayers], lgb[3], lsc;
 };
 
-// C[32×32] = A[32×K]·B[K×32] with A(i,k) = a[i·ars + k·acs], B(k,j) = b[k·brs + j·bcs].
-// Result reg q of lane is C(row(q, lane), lane&31). K is a multiple of 16 (widths padded to
-// 32, mini-batches of 32 rows). An operand whose k index is contiguous in LDS (AK: acs ==
-// 1, BK: brs == 1 — forward: H rows and W rows; backward dH: G rows) is read as two 16-byte
-// ds_read_b128 per 8 k values: row strides are ≡ 4 floats mod 64 banks (make_desc), so the
-// 16-lane groups of a b128 read hit disjoint banks, and every row start and k offset is a
-// multiple of 4 floats. Strided operands are read one float per k.
-//
-// fp32 (v_mfma_f32_32x32x2_f32): for its 8 MFMAs of a 16-wide k step, lane half kh supplies
-// the 8 contiguous k = k0 + 8·kh + u (u = MFMA index) of its row / column in both operands
-// — a permutation of the k sum, so one half's values are one contiguous run.
-template <bool AK, bool BK>
-__device__ __forceinline__ f32x16 wave_gemm32_f32(const float* a, int ars, int acs,
-                                                  const float* b, int brs, int bcs, int K) {
-  const int lane = threadIdx.x & 63;
-  const int r = lane & 31, kh = lane >> 5;
-  f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  const float* ap = a + r * ars + 8 * kh * (AK ? 1 : acs);
-  const float* bp = b + 8 * kh * (BK ? 1 : brs) + r * bcs;
-  for (int k = 0; k < K; k += 16) {
-    float av[8], bv[8];
-    if constexpr (AK) {
-      const float4 x0 = *reinterpret_cast<const float4*>(ap + k);
-      const float4 x1 = *reinterpret_cast<const float4*>(ap + k + 4);
-      av[0] = x0.x; av[1] = x0.y; av[2] = x0.z; av[3] = x0.w;
-      av[4] = x1.x; av[5] = x1.y; av[6] = x1.z; av[7] = x1.w;
-    } else {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) av[u] = ap[(k + u) * acs];
-    }
-    if constexpr (BK) {
-      const float4 y0 = *reinterpret_cast<const float4*>(bp + k);
-      const float4 y1 = *reinterpret_cast<const float4*>(bp + k + 4);
-      bv[0] = y0.x; bv[1] = y0.y; bv[2] = y0.z; bv[3] = y0.w;
-      bv[4] = y1.x; bv[5] = y1.y; bv[6] = y1.z; bv[7] = y1.w;
-    } else {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) bv[u] = bp[(k + u) * brs];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// Mixed precision: the same product with operands rounded to bf16 (RNE) as they leave
-// LDS and fp32 accumulation, on v_mfma_f32_32x32x16_bf16 — K/16 instructions instead
-// of K/2. Operand map: lane l (r = l&31, h = l>>5) supplies A(r, k + 8h + j) and
-// B(k + 8h + j, r), j = 0..7 (already one contiguous run per lane); the C layout is the
-// fp32 form's.
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ short bf16_bits(float v) {
   return __builtin_bit_cast(short, __float2bfloat16(v));
 }
-template <bool CONTIG>
-__device__ __forceinline__ void load8_bf16(const float* p, int stride, int k, bf16x8& o) {
-  if constexpr (CONTIG) {
-    const float4 x0 = *reinterpret_cast<const float4*>(p + k);
-    const float4 x1 = *reinterpret_cast<const float4*>(p + k + 4);
-    o[0] = bf16_bits(x0.x); o[1] = bf16_bits(x0.y); o[2] = bf16_bits(x0.z); o[3] = bf16_bits(x0.w);
-    o[4] = bf16_bits(x1.x); o[5] = bf16_bits(x1.y); o[6] = bf16_bits(x1.z); o[7] = bf16_bits(x1.w);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = bf16_bits(p[(k + j) * stride]);
-  }
-}
-template <bool AK, bool BK>
-__device__ __forceinline__ f32x16 wave_gemm32_bf16(const float* a, int ars, int acs,
-                                                   const float* b, int brs, int bcs, int K) {
-  const int lane = threadIdx.x & 63;
-  const int r = lane & 31, kh = lane >> 5;
-  f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  const float* ap = a + r * ars + 8 * kh * (AK ? 1 : acs);
-  const float* bp = b + 8 * kh * (BK ? 1 : brs) + r * bcs;
-#pragma unroll 2
-  for (int k = 0; k < K; k += 16) {
-    bf16x8 af, bfr;
-    load8_bf16<AK>(ap, acs, k, af);
-    load8_bf16<BK>(bp, brs, k, bfr);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr, acc, 0, 0, 0);
-  }
-  return acc;
-}
 
-#ifndef OMLDM_MLP_VEC
-#define OMLDM_MLP_VEC 3  // diagnostics: bit 0 vector reads of k-contiguous A, bit 1 of B
-#endif
-constexpr bool kVecA = (OMLDM_MLP_VEC & 1) != 0, kVecB = (OMLDM_MLP_VEC & 2) != 0;
-
-template <bool AK, bool BK>
-__device__ __forceinline__ f32x16 wave_gemm32(const float* a, int ars, int acs, const float* b,
-                                              int brs, int bcs, int K, int bf16) {
-  return bf16 ? wave_gemm32_bf16<AK, BK>(a, ars, acs, b, brs, bcs, K)
-              : wave_gemm32_f32<AK, BK>(a, ars, acs, b, brs, bcs, K);
-}
-
-// 16×16 tiles (v_mfma_f32_16x16x4_f32 / v_mfma_f32_16x16x16_bf16): a 32-row mini-batch
-// against 64-wide layers then has 8–16 output tiles per GEMM instead of 2–4, so all four
-// waves of the spoke work in every phase rather than one or two. Lane l (i = l&15,
-// g = l>>4) supplies, per 16-wide k step, the 4 consecutive k = k0 + 4g + u of its A row
-// and B column (one b128 read when k is contiguous in LDS); fp32 MFMA u takes value u
-// (a permutation of the k sum), bf16 takes all four at once. acc[j] = C(4g + j, i).
+// The tile product of every form: C[16×16] = A[16×K]·B[K×16] with A(i,k) = a[i·ars + k·acs],
+// B(k,j) = b[k·brs + j·bcs] in LDS, on v_mfma_f32_16x16x4_f32 / v_mfma_f32_16x16x16_bf16
+// (operands rounded to bf16, RNE, as they leave LDS; fp32 accumulation). A 32-row
+// mini-batch against 64-wide layers is 8–16 such tiles per GEMM, so every wave of the
+// spoke works in every phase. Lane l (i = l&15, g = l>>4) supplies, per 16-wide k step, the
+// 4 consecutive k = k0 + 4g + u of its A row and B column — one b128 read where k is
+// contiguous in LDS (AK: acs == 1, BK: brs == 1), one float per k otherwise; fp32 MFMA u
+// takes value u (a permutation of the k sum), bf16 takes all four at once.
+// acc[j] = C(4g + j, i).
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
-template <bool AK, bool BK>
-__device__ __forceinline__ f32x4 wave_gemm16(const float* a, int ars, int acs, const float* b,
-                                             int brs, int bcs, int K, int bf16) {
+
+// K a multiple of 16: operands read at the top of each 16-wide k step (issued while the
+// previous step's MFMAs are in the pipe), the accumulator chained through the MFMAs in
+// place — no register copies of it between steps (a copy waits for the matrix pipe to
+// drain). BF = 0 / 1: the fp32 / bf16 instantiation (no branch in the loop); BF < 0: one
+// loop that picks per k step by `bf16` (a uniform branch).
+template <bool AK, bool BK, int BF>
+__device__ __forceinline__ f32x4 gemm16t(const float* a, int ars, int acs, const float* b,
+                                         int brs, int bcs, int K, int bf16 = 0) {
   const int lane = threadIdx.x & 63;
   const int r = lane & 15, g = lane >> 4;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -160,20 +91,20 @@ __device__ __forceinline__ f32x4 wave_gemm16(const float* a, int ars, int acs, c
   for (int k = 0; k < K; k += 16) {
     float av[4], bv[4];
     if constexpr (AK) {
-      const float4 x = *reinterpret_cast<const float4*>(ap + k);
-      av[0] = x.x; av[1] = x.y; av[2] = x.z; av[3] = x.w;
+      const float4 t = *reinterpret_cast<const float4*>(ap + k);
+      av[0] = t.x; av[1] = t.y; av[2] = t.z; av[3] = t.w;
     } else {
 #pragma unroll
       for (int u = 0; u < 4; ++u) av[u] = ap[(k + u) * acs];
     }
     if constexpr (BK) {
-      const float4 y = *reinterpret_cast<const float4*>(bp + k);
-      bv[0] = y.x; bv[1] = y.y; bv[2] = y.z; bv[3] = y.w;
+      const float4 t = *reinterpret_cast<const float4*>(bp + k);
+      bv[0] = t.x; bv[1] = t.y; bv[2] = t.z; bv[3] = t.w;
     } else {
 #pragma unroll
       for (int u = 0; u < 4; ++u) bv[u] = bp[(k + u) * brs];
     }
-    if (bf16) {
+    if (BF < 0 ? bf16 != 0 : BF > 0) {
       const bf16x4 af = {bf16_bits(av[0]), bf16_bits(av[1]), bf16_bits(av[2]), bf16_bits(av[3])};
       const bf16x4 bfv = {bf16_bits(bv[0]), bf16_bits(bv[1]), bf16_bits(bv[2]), bf16_bits(bv[3])};
       acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(af, bfv, acc, 0, 0, 0);
@@ -184,31 +115,15 @@ __device__ __forceinline__ f32x4 wave_gemm16(const float* a, int ars, int acs, c
   }
   return acc;
 }
-
-#ifndef OMLDM_MLP_TILE
-#define OMLDM_MLP_TILE 16  // output tile of the round/forward GEMMs: 16 or 32
-#endif
-#if OMLDM_MLP_TILE == 16
-typedef f32x4 AccT;
-constexpr int kT = 16, kQ = 4;
-__device__ __forceinline__ int trow(int q, int lane) { return 4 * (lane >> 4) + q; }
-template <bool AK, bool BK>
-__device__ __forceinline__ AccT tile_gemm(const float* a, int ars, int acs, const float* b, int brs,
-                                          int bcs, int K, int bf16) {
-  return wave_gemm16<AK, BK>(a, ars, acs, b, brs, bcs, K, bf16);
+// INLOOP: the branch on `bf16` inside the k loop (one copy of the loop: the 4-wave round
+// kernel, whose fp32 rounds measured 1.1–1.5 % slower with two: profiles/round8/nn_refactor.md)
+template <bool AK, bool BK, bool INLOOP = false>
+__device__ __forceinline__ f32x4 gemm16p(const float* a, int ars, int acs, const float* b,
+                                         int brs, int bcs, int K, int bf16) {
+  if constexpr (INLOOP) return gemm16t<AK, BK, -1>(a, ars, acs, b, brs, bcs, K, bf16);
+  return bf16 ? gemm16t<AK, BK, 1>(a, ars, acs, b, brs, bcs, K)
+              : gemm16t<AK, BK, 0>(a, ars, acs, b, brs, bcs, K);
 }
-#else
-typedef f32x16 AccT;
-constexpr int kT = 32, kQ = 16;
-__device__ __forceinline__ int trow(int q, int lane) {
-  return (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-}
-template <bool AK, bool BK>
-__device__ __forceinline__ AccT tile_gemm(const float* a, int ars, int acs, const float* b, int brs,
-                                          int bcs, int K, int bf16) {
-  return wave_gemm32<AK, BK>(a, ars, acs, b, brs, bcs, K, bf16);
-}
-#endif
 
 // Activation and its derivative expressed through the activation's OUTPUT h (what the
 // forward pass keeps in LDS): relu' = [h > 0], tanh' = 1 − h², σ' = h(1 − h).
@@ -244,8 +159,10 @@ __device__ void load_model(const float* __restrict__ w, float* sm, const MlpDesc
 }
 
 // Forward of one 32-row tile already staged in H_0; H_L holds the logits.
+template <bool INLOOP>
 __device__ void forward(float* sm, const MlpDesc& g) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int ci = lane & 15, cg = lane >> 4;  // accumulator column / row group
   for (int l = 0; l < g.L; ++l) {
     const float* H = sm + g.lh[l];
     float* Ho = sm + g.lh[l + 1];
@@ -255,16 +172,16 @@ __device__ void forward(float* sm, const MlpDesc& g) {
     const bool hidden = l + 1 < g.L;
     for (int t = wave; t < nt; t += 4) {
       const int rt = t / ntc, ct = t - rt * ntc;
-      const AccT acc = tile_gemm<kVecA, kVecB>(H + rt * kT * g.ldh[l], g.ldh[l], 1,
-                                               W + ct * kT * g.ldw[l], 1, g.ldw[l], g.np[l], g.bf16);
-      const int col = ct * kT + (lane & (kT - 1));
+      const f32x4 acc = gemm16p<true, true, INLOOP>(H + rt * kT * g.ldh[l], g.ldh[l], 1,
+                                            W + ct * kT * g.ldw[l], 1, g.ldw[l], g.np[l], g.bf16);
+      const int col = ct * kT + ci;
       const float bias = bs[col];
       const bool pad = col >= g.n[l + 1];  // padding columns stay exactly zero
 #pragma unroll
-      for (int q = 0; q < kQ; ++q) {
+      for (int q = 0; q < 4; ++q) {
         float v = acc[q] + bias;
         if (hidden) v = pad ? 0.f : act_fwd(v, g.act);
-        Ho[(rt * kT + trow(q, lane)) * ldo + col] = v;
+        Ho[(rt * kT + 4 * cg + q) * ldo + col] = v;
       }
     }
     __syncthreads();
@@ -279,6 +196,90 @@ __device__ void stage_rows(const float* __restrict__ x, long long r0, long long 
     const int r = i / np0, c = i - r * np0;
     const long long row = r0 + r;
     H[r * ld + c] = (row < r1 && c < n0) ? x[row * n0 + c] : 0.f;
+  }
+}
+
+// Mini-batch staging of the fused round kernels (NT threads): H_0 and the labels of the
+// step at m0, with the NEXT mini-batch's loads in flight while the current one trains
+// (np0 ≤ 64: kSlots slots of the 32 × np0 tile per thread, fixed (row, col) per slot, held
+// in registers); wider inputs stage synchronously. Rows past r1 read as zero, their labels
+// as NaN. The caller's barrier follows.
+template <int NT>
+struct RowStager {
+  static constexpr int kSlots = (kMB * 64 + NT - 1) / NT;
+  bool pf;
+  int n0;
+  int soff[kSlots], srow[kSlots], scol[kSlots];
+  float xr[kSlots], yr;
+
+  __device__ __forceinline__ void init(const MlpDesc& g) {
+    const int tid = threadIdx.x, np0 = g.np[0], ld0 = g.ldh[0];
+    n0 = g.n[0];
+    pf = np0 <= 64;
+    yr = 0.f;
+#pragma unroll
+    for (int j = 0; j < kSlots; ++j) {
+      const int i = tid + NT * j;
+      const bool in = pf && i < kMB * np0;
+      srow[j] = in ? i / np0 : -1;
+      scol[j] = in ? i - srow[j] * np0 : 0;
+      soff[j] = in ? srow[j] * ld0 + scol[j] : 0;
+    }
+  }
+  // unconditional loads from clamped rows
+  __device__ __forceinline__ void fetch(const float* __restrict__ x, const float* __restrict__ yv,
+                                        long long m, long long r1) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < kSlots; ++j) {
+      const long long row = min(m + (srow[j] < 0 ? 0 : srow[j]), r1 - 1);
+      xr[j] = x[row * n0 + (scol[j] < n0 ? scol[j] : 0)];
+    }
+    yr = yv[min(m + (tid < kMB ? tid : 0), r1 - 1)];
+  }
+  __device__ __forceinline__ void stage(const float* __restrict__ x, const float* __restrict__ yv,
+                                        long long m0, long long r1, float* sm, const MlpDesc& g) {
+    const int tid = threadIdx.x;
+    if (pf) {
+      float* H = sm + g.lh[0];
+#pragma unroll
+      for (int j = 0; j < kSlots; ++j)
+        if (srow[j] >= 0) H[soff[j]] = (m0 + srow[j] < r1 && scol[j] < n0) ? xr[j] : 0.f;
+      if (tid < kMB) sm[g.ly + tid] = m0 + tid < r1 ? yr : __builtin_nanf("");
+      if (m0 + kMB < r1) fetch(x, yv, m0 + kMB, r1);
+    } else {
+      stage_rows(x, m0, r1, sm, g);
+      if (tid < kMB) {
+        const long long row = m0 + tid;
+        sm[g.ly + tid] = row < r1 ? yv[row] : __builtin_nanf("");
+      }
+    }
+  }
+};
+
+// Round end of the fused kernels: Δ = W_spoke − W_0. With a workspace: the spoke's own row,
+// plain coalesced stores (mlp_colsum_kernel sums the rows); without: atomics into the
+// accumulator (every spoke hits the same nparams addresses — the slow fallback).
+template <int NT>
+__device__ __forceinline__ void store_delta(const float* __restrict__ w, const float* sm,
+                                            const MlpDesc& g, float* __restrict__ dacc,
+                                            float* __restrict__ ws, int nparams) {
+  const int tid = threadIdx.x;
+  float* wrow = ws ? ws + (size_t)blockIdx.x * nparams : nullptr;
+  for (int l = 0; l < g.L; ++l) {
+    const int nin = g.n[l], nout = g.n[l + 1], ld = g.ldw[l];
+    const float* W = sm + g.lw[l];
+    for (int i = tid; i < nout * nin; i += NT) {
+      const int o = i / nin, c = i - o * nin;
+      const float d = W[o * ld + c] - w[g.woff[l] + i];
+      if (wrow) wrow[g.woff[l] + i] = d;
+      else if (d != 0.f) atomicAdd(&dacc[g.woff[l] + i], d);
+    }
+    for (int o = tid; o < nout; o += NT) {
+      const float d = sm[g.lb[l] + o] - w[g.boff[l] + o];
+      if (wrow) wrow[g.boff[l] + o] = d;
+      else if (d != 0.f) atomicAdd(&dacc[g.boff[l] + o], d);
+    }
   }
 }
 
@@ -317,61 +318,26 @@ __global__ __launch_bounds__(256) void mlp_round_kernel(const float* __restrict_
                                                         float* __restrict__ ws, int nparams) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int ci = lane & 15, cg = lane >> 4;  // accumulator column / row group
   const long long r0 = (long long)blockIdx.x * R;
   const long long r1 = min(B, r0 + R);
   if (r0 >= B) return;
   load_model(w, sm, g);
   float loss = 0.f, corr = 0.f, nv = 0.f;
   const int L = g.L, npL = g.np[L];
-  // Row staging with the NEXT mini-batch's loads in flight while the current one trains
-  // (np0 ≤ 64: ≤ 8 slots of the 32 × np0 tile per thread, fixed (row, col) per slot);
-  // wider inputs stage synchronously.
-  constexpr int kSlots = 8;
-  const int np0 = g.np[0], n0 = g.n[0], ld0 = g.ldh[0];
-  const bool pf = np0 <= 64;
-  int soff[kSlots], srow[kSlots], scol[kSlots];
-#pragma unroll
-  for (int j = 0; j < kSlots; ++j) {
-    const int i = tid + 256 * j;
-    const bool in = pf && i < kMB * np0;
-    srow[j] = in ? i / np0 : -1;
-    scol[j] = in ? i - srow[j] * np0 : 0;
-    soff[j] = in ? srow[j] * ld0 + scol[j] : 0;
-  }
-  float xr[kSlots];
-  float yr = 0.f;
-  auto fetch = [&](long long m) {  // unconditional loads from clamped rows
-#pragma unroll
-    for (int j = 0; j < kSlots; ++j) {
-      const long long row = min(m + (srow[j] < 0 ? 0 : srow[j]), r1 - 1);
-      xr[j] = x[row * n0 + (scol[j] < n0 ? scol[j] : 0)];
-    }
-    yr = yv[min(m + (tid < kMB ? tid : 0), r1 - 1)];
-  };
-  if (pf) fetch(r0);
+  RowStager<256> rows;
+  rows.init(g);
+  if (rows.pf) rows.fetch(x, yv, r0, r1);
 #ifdef OMLDM_MLP_STAMPS
   unsigned long long mlp_t_ = clock64();
   unsigned long long mlp_acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
   for (long long m0 = r0; m0 < r1; m0 += kMB) {
     MLP_STAMP(0);
-    if (pf) {
-      float* H = sm + g.lh[0];
-#pragma unroll
-      for (int j = 0; j < kSlots; ++j)
-        if (srow[j] >= 0) H[soff[j]] = (m0 + srow[j] < r1 && scol[j] < n0) ? xr[j] : 0.f;
-      if (tid < kMB) sm[g.ly + tid] = m0 + tid < r1 ? yr : __builtin_nanf("");
-      if (m0 + kMB < r1) fetch(m0 + kMB);
-    } else {
-      stage_rows(x, m0, r1, sm, g);
-      if (tid < kMB) {
-        const long long row = m0 + tid;
-        sm[g.ly + tid] = row < r1 ? yv[row] : __builtin_nanf("");
-      }
-    }
+    rows.stage(x, yv, m0, r1, sm, g);
     __syncthreads();
     MLP_STAMP(1);
-    forward(sm, g);
+    forward<true>(sm, g);
     MLP_STAMP(2);
     // ---- loss gradient dZ_L (one thread per row)
     bool valid = false;
@@ -426,12 +392,12 @@ __global__ __launch_bounds__(256) void mlp_round_kernel(const float* __restrict_
         const int ntc = nin / kT;
         for (int t = wave; t < (kMB / kT) * ntc; t += 4) {
           const int rt = t / ntc, ct = t - rt * ntc;
-          const AccT acc = tile_gemm<kVecA, false>(Gc + rt * kT * g.ldg, g.ldg, 1, W + ct * kT, ldw,
-                                                   1, nout, g.bf16);
-          const int col = ct * kT + (lane & (kT - 1));
+          const f32x4 acc = gemm16p<true, false, true>(Gc + rt * kT * g.ldg, g.ldg, 1, W + ct * kT, ldw,
+                                                 1, nout, g.bf16);
+          const int col = ct * kT + ci;
 #pragma unroll
-          for (int q = 0; q < kQ; ++q) {
-            const int row = rt * kT + trow(q, lane);
+          for (int q = 0; q < 4; ++q) {
+            const int row = rt * kT + 4 * cg + q;
             Gn[row * g.ldg + col] = acc[q] * act_grad(H[row * ldh + col], g.act);
           }
         }
@@ -441,12 +407,12 @@ __global__ __launch_bounds__(256) void mlp_round_kernel(const float* __restrict_
       const int ntc = nin / kT, nto = nout / kT;
       for (int t = wave; t < nto * ntc; t += 4) {
         const int to = t / ntc, tc = t - to * ntc;
-        const AccT acc =
-            tile_gemm<false, false>(Gc + to * kT, 1, g.ldg, H + tc * kT, ldh, 1, kMB, g.bf16);
-        const int c = tc * kT + (lane & (kT - 1));
+        const f32x4 acc =
+            gemm16p<false, false, true>(Gc + to * kT, 1, g.ldg, H + tc * kT, ldh, 1, kMB, g.bf16);
+        const int c = tc * kT + ci;
 #pragma unroll
-        for (int q = 0; q < kQ; ++q) {
-          const int o = to * kT + trow(q, lane);
+        for (int q = 0; q < 4; ++q) {
+          const int o = to * kT + 4 * cg + q;
           W[o * ldw + c] -= eta * acc[q];
         }
       }
@@ -465,25 +431,7 @@ __global__ __launch_bounds__(256) void mlp_round_kernel(const float* __restrict_
     MLP_STAMP(4);
   }
   MLP_STAMP_FLUSH();
-  // ---- round end: Δ = W_spoke − W_0. With a workspace: the spoke's own row, plain
-  // coalesced stores (mlp_colsum_kernel sums the rows); without: atomics into the
-  // accumulator (every spoke hits the same nparams addresses — the slow fallback).
-  float* wrow = ws ? ws + (size_t)blockIdx.x * nparams : nullptr;
-  for (int l = 0; l < L; ++l) {
-    const int nin = g.n[l], nout = g.n[l + 1], ld = g.ldw[l];
-    const float* W = sm + g.lw[l];
-    for (int i = tid; i < nout * nin; i += blockDim.x) {
-      const int o = i / nin, c = i - o * nin;
-      const float d = W[o * ld + c] - w[g.woff[l] + i];
-      if (wrow) wrow[g.woff[l] + i] = d;
-      else if (d != 0.f) atomicAdd(&dacc[g.woff[l] + i], d);
-    }
-    for (int o = tid; o < nout; o += blockDim.x) {
-      const float d = sm[g.lb[l] + o] - w[g.boff[l] + o];
-      if (wrow) wrow[g.boff[l] + o] = d;
-      else if (d != 0.f) atomicAdd(&dacc[g.boff[l] + o], d);
-    }
-  }
+  store_delta<256>(w, sm, g, dacc, ws, nparams);
   if (wave == 0) {
     loss = wave_sum(loss);
     corr = wave_sum(corr);
@@ -517,51 +465,6 @@ __global__ __launch_bounds__(256) void mlp_round_kernel(const float* __restrict_
 // * operand loads of the next 16-wide k step are issued before the current MFMAs.
 // Same arithmetic as v1 (fp32 MFMA, same mini-batch order); sums may associate
 // differently.
-// One 16×16 tile, K a multiple of 16: operands read at the top of each 16-wide k step
-// (issued while the previous step's MFMAs are in the pipe), the accumulator chained through
-// the MFMAs in place — no register copies of it between steps (a copy waits for the
-// matrix pipe to drain). fp32 and bf16 are separate instantiations (no branch in the loop).
-template <bool AK, bool BK, bool BF16>
-__device__ __forceinline__ f32x4 gemm16t(const float* a, int ars, int acs, const float* b,
-                                         int brs, int bcs, int K) {
-  const int lane = threadIdx.x & 63;
-  const int r = lane & 15, g = lane >> 4;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const float* ap = a + r * ars + 4 * g * (AK ? 1 : acs);
-  const float* bp = b + 4 * g * (BK ? 1 : brs) + r * bcs;
-  for (int k = 0; k < K; k += 16) {
-    float av[4], bv[4];
-    if constexpr (AK) {
-      const float4 t = *reinterpret_cast<const float4*>(ap + k);
-      av[0] = t.x; av[1] = t.y; av[2] = t.z; av[3] = t.w;
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) av[u] = ap[(k + u) * acs];
-    }
-    if constexpr (BK) {
-      const float4 t = *reinterpret_cast<const float4*>(bp + k);
-      bv[0] = t.x; bv[1] = t.y; bv[2] = t.z; bv[3] = t.w;
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) bv[u] = bp[(k + u) * brs];
-    }
-    if constexpr (BF16) {
-      const bf16x4 af = {bf16_bits(av[0]), bf16_bits(av[1]), bf16_bits(av[2]), bf16_bits(av[3])};
-      const bf16x4 bfv = {bf16_bits(bv[0]), bf16_bits(bv[1]), bf16_bits(bv[2]), bf16_bits(bv[3])};
-      acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(af, bfv, acc, 0, 0, 0);
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);
-    }
-  }
-  return acc;
-}
-template <bool AK, bool BK>
-__device__ __forceinline__ f32x4 gemm16p(const float* a, int ars, int acs, const float* b,
-                                         int brs, int bcs, int K, int bf16) {
-  return bf16 ? gemm16t<AK, BK, true>(a, ars, acs, b, brs, bcs, K)
-              : gemm16t<AK, BK, false>(a, ars, acs, b, brs, bcs, K);
-}
 
 // 16-lane DPP row reductions (every lane of the row gets the result)
 __device__ __forceinline__ float row16_max(float v) {
@@ -583,13 +486,14 @@ __device__ __forceinline__ float row16_min(float v) {
   return fminf(v, dpp_mov<0x128>(v));
 }
 
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void mlp_round2_kernel(
+constexpr int kRound2Waves = 16;
+
+__global__ __launch_bounds__(kRound2Waves * 64) void mlp_round2_kernel(
     const float* __restrict__ w, const float* __restrict__ x, const float* __restrict__ yv,
     long long B, int R, float lr, float* __restrict__ dacc, float* __restrict__ stats,
     float* __restrict__ nact, MlpDesc g, float* __restrict__ ws, int nparams) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  constexpr int NT = NW * 64;
+  constexpr int NW = kRound2Waves, NT = NW * 64;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int ci = lane & 15, cg = lane >> 4;  // accumulator column / row group
   const long long r0 = (long long)blockIdx.x * R;
@@ -602,30 +506,9 @@ __global__ __launch_bounds__(NW * 64) void mlp_round2_kernel(
   if (tid < 4) sm[g.lsc + tid] = 0.f;
   float loss = 0.f, corr = 0.f, nv = 0.f;
   auto gb = [&](int j) { return sm + g.lgb[j % 3]; };
-  // staging: the next mini-batch's rows in registers while the current one trains
-  constexpr int kSlots = (kMB * 64 + NT - 1) / NT;
-  const int np0 = g.np[0], n0 = g.n[0], ld0 = g.ldh[0];
-  const bool pf = np0 <= 64;
-  int soff[kSlots], srow[kSlots], scol[kSlots];
-#pragma unroll
-  for (int j = 0; j < kSlots; ++j) {
-    const int i = tid + NT * j;
-    const bool in = pf && i < kMB * np0;
-    srow[j] = in ? i / np0 : -1;
-    scol[j] = in ? i - srow[j] * np0 : 0;
-    soff[j] = in ? srow[j] * ld0 + scol[j] : 0;
-  }
-  float xr[kSlots];
-  float yr = 0.f;
-  auto fetch = [&](long long m) {
-#pragma unroll
-    for (int j = 0; j < kSlots; ++j) {
-      const long long row = min(m + (srow[j] < 0 ? 0 : srow[j]), r1 - 1);
-      xr[j] = x[row * n0 + (scol[j] < n0 ? scol[j] : 0)];
-    }
-    yr = yv[min(m + (tid < kMB ? tid : 0), r1 - 1)];
-  };
-  if (pf) fetch(r0);
+  RowStager<NT> rows;
+  rows.init(g);
+  if (rows.pf) rows.fetch(x, yv, r0, r1);
   __syncthreads();
 #ifdef OMLDM_MLP_STAMPS
   unsigned long long mlp_t_ = clock64();
@@ -633,20 +516,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_round2_kernel(
 #endif
   for (long long m0 = r0; m0 < r1; m0 += kMB) {
     MLP_STAMP(0);
-    if (pf) {
-      float* H = sm + g.lh[0];
-#pragma unroll
-      for (int j = 0; j < kSlots; ++j)
-        if (srow[j] >= 0) H[soff[j]] = (m0 + srow[j] < r1 && scol[j] < n0) ? xr[j] : 0.f;
-      if (tid < kMB) sm[g.ly + tid] = m0 + tid < r1 ? yr : __builtin_nanf("");
-      if (m0 + kMB < r1) fetch(m0 + kMB);
-    } else {
-      stage_rows(x, m0, r1, sm, g);
-      if (tid < kMB) {
-        const long long row = m0 + tid;
-        sm[g.ly + tid] = row < r1 ? yv[row] : __builtin_nanf("");
-      }
-    }
+    rows.stage(x, yv, m0, r1, sm, g);
     __syncthreads();
     // valid rows of the step: every wave counts them itself
     const float yl = sm[g.ly + (lane & 31)];
@@ -783,23 +653,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_round2_kernel(
     }
   }
   MLP_STAMP_FLUSH();
-  // ---- round end: Δ = W_spoke − W_0 (as v1)
-  float* wrow = ws ? ws + (size_t)blockIdx.x * nparams : nullptr;
-  for (int l = 0; l < L; ++l) {
-    const int nin = g.n[l], nout = g.n[l + 1], ld = g.ldw[l];
-    const float* W = sm + g.lw[l];
-    for (int i = tid; i < nout * nin; i += NT) {
-      const int o = i / nin, c = i - o * nin;
-      const float d = W[o * ld + c] - w[g.woff[l] + i];
-      if (wrow) wrow[g.woff[l] + i] = d;
-      else if (d != 0.f) atomicAdd(&dacc[g.woff[l] + i], d);
-    }
-    for (int o = tid; o < nout; o += NT) {
-      const float d = sm[g.lb[l] + o] - w[g.boff[l] + o];
-      if (wrow) wrow[g.boff[l] + o] = d;
-      else if (d != 0.f) atomicAdd(&dacc[g.boff[l] + o], d);
-    }
-  }
+  store_delta<NT>(w, sm, g, dacc, ws, nparams);
   loss = wave_sum(loss);
   corr = wave_sum(corr);
   nv = wave_sum(nv);
@@ -830,7 +684,7 @@ __global__ __launch_bounds__(256) void mlp_forward_kernel(const float* __restric
     __syncthreads();  // previous tile's H_L consumed
     stage_rows(x, m0, B, sm, g);
     __syncthreads();
-    forward(sm, g);
+    forward<false>(sm, g);
     const float* o = sm + g.lh[L];
     for (int i = threadIdx.x; i < kMB * g.K; i += blockDim.x) {
       const int r = i / g.K, k = i - r * g.K;
@@ -1387,17 +1241,21 @@ static int make_stream_desc(int L, const int* widths, int task, int act, MlpStre
 
 using namespace omldm;
 
-// Round kernel form: 0 v1 (mlp_round_kernel), 1 / 2 / 3 v2 with 4 / 8 / 16 waves (v2 takes
-// output widths ≤ 16), 4 the streamed-weight form at every shape it takes, also where a fused
-// form fits (tests and benchmarks; it applies to omldm_mlp_forward too). Whatever the form, a
-// stack no fused kernel holds goes to the streamed form. `set` ≥ 0 sets it; the default
-// comes from OMLDM_MLP_FORM (3).
+// Round kernel form: 0 fused-32 (v1) wherever a fused kernel runs, 3 (the default) fused-16
+// (v2) where it applies, 4 the streamed-weight form at every shape it takes, also where a
+// fused form fits (tests and benchmarks; it applies to omldm_mlp_forward too). Whatever the
+// form, a stack no fused kernel holds goes to the streamed form. `set` ∈ {0, 3, 4} sets it,
+// any other value only reads it; the default comes from OMLDM_MLP_FORM (3, also for any
+// other value there). (1 and 2 were 4- and 8-wave fused-16 kernels: docs/KERNELS.md.)
+static bool mlp_form_known(int form) { return form == 0 || form == 3 || form == 4; }
+
 OMLDM_API int omldm_mlp_form(int set) {
   static int form = [] {
     const char* e = getenv("OMLDM_MLP_FORM");
-    return e ? atoi(e) : 3;
+    const int f = e ? atoi(e) : 3;
+    return mlp_form_known(f) ? f : 3;
   }();
-  if (set >= 0) form = set;
+  if (mlp_form_known(set)) form = set;
   return form;
 }
 
@@ -1415,16 +1273,61 @@ OMLDM_API long long omldm_mlp_stream_lds_bytes(int L, const int* widths) {
   return (long long)g.total * 4;
 }
 
-constexpr size_t kMlpLdsMax = 160 * 1024;
+// LDS bytes of the fused-16 layout; -1 where fused-16 does not apply (output width > 16).
+OMLDM_API long long omldm_mlp_fused16_lds_bytes(int L, const int* widths) {
+  MlpDesc g;
+  if (make_desc(L, widths, 0, 0, &g, 16) || widths[L] > 16) return -1;
+  return (long long)g.total * 4;
+}
+
+constexpr size_t kMlpLdsMax = 160 * 1024;  // LDS of one CU: every form's limit
+
+enum { kMlpFused32 = 0, kMlpFused16 = 1, kMlpStream = 2 };  // kernel ids of a plan
+
+// The routing of omldm_mlp_round and omldm_mlp_forward (host code only; both launchers
+// consume it and decide nothing themselves): which kernels take the layer stack under `form`
+// (< 0: the form in use). out = {round kernel, its waves, its LDS bytes, forward kernel, its
+// LDS bytes}. 0: out is filled; −1: not a layer stack (layer count, a width < 1 or past the
+// streamed form's index range); −2: no form holds it.
+// * round: fused-16 for output widths ≤ 16 whose 16-padded layout fits (not under form 0),
+//   else fused-32 if the 32-padded layout fits — which also takes the output-≤-16 stacks
+//   that fit padded to 32 but not with fused-16's third gradient buffer and bias gradients
+//   — else streamed; form 4 streams everything;
+// * forward: the fused kernel whenever the 32-padded layout fits, whatever trains the stack;
+//   else (and under form 4) streamed, refused past the ROUND's activation limit so that one
+//   limit holds for training and scoring.
+OMLDM_API int omldm_mlp_plan(int L, const int* widths, int form, int* out) {
+  for (int i = 0; i < 5; ++i) out[i] = 0;
+  if (!mlp_form_known(form)) form = omldm_mlp_form(-1);
+  MlpDesc g32, g16;
+  MlpStreamDesc gs;
+  if (make_desc(L, widths, 0, 0, &g32)) return -1;
+  const size_t lds32 = (size_t)g32.total * 4;
+  const bool fits32 = lds32 <= kMlpLdsMax;
+  const bool fits16 = form == 3 && widths[L] <= 16 && make_desc(L, widths, 0, 0, &g16, 16) == 0 &&
+                      (size_t)g16.total * 4 <= kMlpLdsMax;
+  const int round = form == 4 ? kMlpStream : fits16 ? kMlpFused16 : fits32 ? kMlpFused32 : kMlpStream;
+  const int fwd = form == 4 || !fits32 ? kMlpStream : kMlpFused32;
+  if (round == kMlpStream || fwd == kMlpStream) {
+    if (make_stream_desc(L, widths, 0, 0, &gs)) return -1;
+    if ((size_t)gs.total * 4 > kMlpLdsMax) return -2;
+  }
+  out[0] = round;
+  out[1] = round == kMlpFused32 ? 4 : round == kMlpFused16 ? kRound2Waves : kStreamWaves;
+  out[2] = round == kMlpFused32 ? (int)lds32 : round == kMlpFused16 ? g16.total * 4 : gs.total * 4;
+  out[3] = fwd;
+  out[4] = fwd == kMlpFused32 ? (int)lds32 : gs.fwd_total * 4;
+  return 0;
+}
+
+static bool mlp_act_known(int act) { return (act & 0xff) <= kIdentity && !(act & ~0x1ff); }
 
 static int launch_round_stream(const float* w, const float* x, const float* y, long long B, int R,
                                int S, int L, const int* widths, int task, int act, float lr,
-                               float* dacc, float* stats, float* nact, float* ws,
+                               size_t lds, float* dacc, float* stats, float* nact, float* ws,
                                hipStream_t stream) {
   MlpStreamDesc g;
   if (make_stream_desc(L, widths, task, act, &g)) return -1;
-  const size_t lds = (size_t)g.total * 4;
-  if (lds > kMlpLdsMax) return -2;
   if (!ws) return -4;  // the working models live in the scratch rows
   const int e = check_dyn_lds((const void*)mlp_round_stream_kernel, lds);
   if (e) return e;
@@ -1448,42 +1351,30 @@ OMLDM_API int omldm_mlp_round(const float* w, const float* x, const float* y, lo
                               float* dacc, float* stats, float* nact, float* ws, void* stream) {
   if (B <= 0 || S <= 0) return 0;
   if (R <= 0 || (long long)R * S < B) return -3;
+  int plan[5];
+  if (!mlp_act_known(act)) return -1;
+  if (const int rc = omldm_mlp_plan(L, widths, -1, plan)) return rc;
+  const size_t lds = (size_t)plan[2];
+  const dim3 block(plan[1] * 64);
   MlpDesc g;
-  const int form = omldm_mlp_form(-1);
-  if (form == 4)
-    return launch_round_stream(w, x, y, B, R, S, L, widths, task, act, lr, dacc, stats, nact, ws,
-                               (hipStream_t)stream);
-  if (form > 0 && widths[L] <= 16 && make_desc(L, widths, task, act, &g, 16) == 0 &&
-      (size_t)g.total * 4 <= 160 * 1024) {
-    const size_t lds = (size_t)g.total * 4;
-    const int nparams = g.boff[g.L - 1] + g.n[g.L];
-    int e;
-    if (form == 3) {
-      if ((e = check_dyn_lds((const void*)mlp_round2_kernel<16>, lds))) return e;
-      hipLaunchKernelGGL(mlp_round2_kernel<16>, dim3(S), dim3(1024), lds, (hipStream_t)stream, w,
-                         x, y, B, R, lr, dacc, stats, nact, g, ws, nparams);
-    } else if (form == 2) {
-      if ((e = check_dyn_lds((const void*)mlp_round2_kernel<8>, lds))) return e;
-      hipLaunchKernelGGL(mlp_round2_kernel<8>, dim3(S), dim3(512), lds, (hipStream_t)stream, w, x,
-                         y, B, R, lr, dacc, stats, nact, g, ws, nparams);
-    } else {
-      if ((e = check_dyn_lds((const void*)mlp_round2_kernel<4>, lds))) return e;
-      hipLaunchKernelGGL(mlp_round2_kernel<4>, dim3(S), dim3(256), lds, (hipStream_t)stream, w, x,
-                         y, B, R, lr, dacc, stats, nact, g, ws, nparams);
-    }
-  } else {
-    if (make_desc(L, widths, task, act, &g)) return -1;
-    const size_t lds = (size_t)g.total * 4;
-    if (lds > 160 * 1024)
-      return launch_round_stream(w, x, y, B, R, S, L, widths, task, act, lr, dacc, stats, nact, ws,
-                                 (hipStream_t)stream);
-    int e = check_dyn_lds((const void*)mlp_round_kernel, lds);
-    if (e) return e;
-    const int nparams = g.boff[g.L - 1] + g.n[g.L];
-    hipLaunchKernelGGL(mlp_round_kernel, dim3(S), dim3(256), lds, (hipStream_t)stream, w, x, y, B,
-                       R, lr, dacc, stats, nact, g, ws, nparams);
+  int e;
+  switch (plan[0]) {
+    case kMlpStream:
+      return launch_round_stream(w, x, y, B, R, S, L, widths, task, act, lr, lds, dacc, stats, nact,
+                                 ws, (hipStream_t)stream);
+    case kMlpFused16:
+      if (make_desc(L, widths, task, act, &g, 16)) return -1;
+      if ((e = check_dyn_lds((const void*)mlp_round2_kernel, lds))) return e;
+      hipLaunchKernelGGL(mlp_round2_kernel, dim3(S), block, lds, (hipStream_t)stream, w, x, y, B, R,
+                         lr, dacc, stats, nact, g, ws, g.boff[L - 1] + g.n[L]);
+      break;
+    default:  // kMlpFused32
+      if (make_desc(L, widths, task, act, &g)) return -1;
+      if ((e = check_dyn_lds((const void*)mlp_round_kernel, lds))) return e;
+      hipLaunchKernelGGL(mlp_round_kernel, dim3(S), block, lds, (hipStream_t)stream, w, x, y, B, R,
+                         lr, dacc, stats, nact, g, ws, g.boff[L - 1] + g.n[L]);
   }
-  const int nparams = g.boff[g.L - 1] + g.n[g.L];
+  const int nparams = g.boff[L - 1] + g.n[L];
   if (ws)
     hipLaunchKernelGGL(mlp_colsum_kernel, dim3((nparams + 255) / 256, (S + kMlpSlab - 1) / kMlpSlab),
                        dim3(256), 0, (hipStream_t)stream, ws, S, nparams, dacc);
@@ -1493,25 +1384,29 @@ OMLDM_API int omldm_mlp_round(const float* w, const float* x, const float* y, lo
 OMLDM_API int omldm_mlp_forward(const float* w, const float* x, long long B, int L,
                                 const int* widths, int act, float* out, void* stream) {
   if (B <= 0) return 0;
-  MlpDesc g;
-  if (make_desc(L, widths, 0, act, &g)) return -1;
-  const size_t lds = (size_t)g.total * 4;
-  long long tiles = (B + kMB - 1) / kMB;
-  int blocks = (int)(tiles < 1024 ? tiles : 1024);
-  if (lds > 160 * 1024 || omldm_mlp_form(-1) == 4) {  // streamed weights
-    MlpStreamDesc sg;
-    if (make_stream_desc(L, widths, 0, act, &sg)) return -1;
-    const size_t slds = (size_t)sg.fwd_total * 4;
-    if ((size_t)sg.total * 4 > kMlpLdsMax) return -2;  // one limit for training and scoring
-    int e = check_dyn_lds((const void*)mlp_forward_stream_kernel, slds);
-    if (e) return e;
-    hipLaunchKernelGGL(mlp_forward_stream_kernel, dim3(blocks), dim3(kStreamFwdWaves * 64), slds,
-                       (hipStream_t)stream, w, x, B, out, sg);
-    return (int)hipGetLastError();
+  int plan[5];
+  if (!mlp_act_known(act)) return -1;
+  if (const int rc = omldm_mlp_plan(L, widths, -1, plan)) return rc;
+  const size_t lds = (size_t)plan[4];
+  const long long tiles = (B + kMB - 1) / kMB;
+  const int blocks = (int)(tiles < 1024 ? tiles : 1024);
+  int e;
+  switch (plan[3]) {
+    case kMlpStream: {
+      MlpStreamDesc sg;
+      if (make_stream_desc(L, widths, 0, act, &sg)) return -1;
+      if ((e = check_dyn_lds((const void*)mlp_forward_stream_kernel, lds))) return e;
+      hipLaunchKernelGGL(mlp_forward_stream_kernel, dim3(blocks), dim3(kStreamFwdWaves * 64), lds,
+                         (hipStream_t)stream, w, x, B, out, sg);
+      break;
+    }
+    default: {  // kMlpFused32
+      MlpDesc g;
+      if (make_desc(L, widths, 0, act, &g)) return -1;
+      if ((e = check_dyn_lds((const void*)mlp_forward_kernel, lds))) return e;
+      hipLaunchKernelGGL(mlp_forward_kernel, dim3(blocks), dim3(256), lds, (hipStream_t)stream, w,
+                         x, B, out, g);
+    }
   }
-  int e = check_dyn_lds((const void*)mlp_forward_kernel, lds);
-  if (e) return e;
-  hipLaunchKernelGGL(mlp_forward_kernel, dim3(blocks), dim3(256), lds, (hipStream_t)stream, w, x,
-                     B, out, g);
   return (int)hipGetLastError();
 }

@@ -25,7 +25,9 @@
 int main(int argc, char** argv) {
   const int S = argc > 1 ? atoi(argv[1]) : 512;
   const int bf16 = argc > 2 ? atoi(argv[2]) : 1;
-  if (argc > 3) omldm_mlp_form(atoi(argv[3]));  // 0 v1 (phase stamps), 1 / 2 v2 (4 / 8 waves)
+  // 0 v1 (mlp_round_kernel's phases), 3 v2 (mlp_round2_kernel's, the default); the streamed
+  // form (4) carries no stamps
+  if (argc > 3) omldm_mlp_form(atoi(argv[3]));
   const long long B = 131072;
   const int R = (int)(B / S);
   const int widths[4] = {13, 64, 64, 1};
@@ -73,7 +75,12 @@ int main(int argc, char** argv) {
   std::vector<unsigned long long> st((size_t)S * 8);
   CK(hipMemcpy(st.data(), stamps, st.size() * 8, hipMemcpyDeviceToHost));
   printf("S=%d R=%d bf16=%d: round (+colsum) best %.1f us\n", S, R, bf16, best * 1000.f);
-  const bool v2 = omldm_mlp_form(-1) > 0;
+  int plan[5];
+  if (omldm_mlp_plan(L, widths, -1, plan) || plan[0] == kMlpStream) {
+    fprintf(stderr, "form %d has no phase stamps for this stack\n", omldm_mlp_form(-1));
+    return 1;
+  }
+  const bool v2 = plan[0] == kMlpFused16;
   const char* ph1[] = {"", "stage+barrier", "forward", "loss", "backward rest", "bwd dH+sync",
                        "bwd W update", "bwd bias+sync"};
   const char* ph2[] = {"", "stage+barrier+cnt", "hidden forward", "output+loss", "bwd phase 0",

@@ -422,7 +422,7 @@ def mlp_lds_bytes(widths: list[int]) -> int:
     return int(native.hip().omldm_mlp_lds_bytes(len(widths) - 1, _widths_arr(widths)))
 
 
-MLP_LDS_BUDGET = 160 * 1024   # LDS of one CU (gfx950)
+MLP_LDS_BUDGET = 160 * 1024   # LDS of one CU (gfx950); the launcher's plan applies it
 
 
 def mlp_stream_lds_bytes(widths: list[int]) -> int:
@@ -431,13 +431,33 @@ def mlp_stream_lds_bytes(widths: list[int]) -> int:
     return int(native.hip().omldm_mlp_stream_lds_bytes(len(widths) - 1, _widths_arr(widths)))
 
 
+def mlp_fused16_lds_bytes(widths: list[int]) -> int:
+    """LDS of the fused-16 layout (widths padded to 16); -1 for an output wider than 16."""
+    return int(native.hip().omldm_mlp_fused16_lds_bytes(len(widths) - 1, _widths_arr(widths)))
+
+
+MLP_KERNELS = ("fused32", "fused16", "stream")  # csrc/kernels/mlp.hip kMlp*
+
+
+def mlp_plan(widths: list[int], form: int = -1) -> tuple | None:
+    """The kernels the launchers pick for the layer stack under ``form`` (< 0: the form in
+    use), from their own routing (host code, no launch): ``(round kernel, its waves, its
+    LDS bytes, forward kernel, its LDS bytes)`` with kernels ``"fused32"`` (v1), ``"fused16"``
+    (v2) or ``"stream"``; None where no form takes the stack."""
+    import ctypes
+
+    if not 1 <= len(widths) - 1 <= MLP_MAX_LAYERS:
+        return None
+    out = (ctypes.c_int * 5)()
+    if native.hip().omldm_mlp_plan(len(widths) - 1, _widths_arr(widths), int(form), out):
+        return None
+    return (MLP_KERNELS[out[0]], out[1], out[2], MLP_KERNELS[out[3]], out[4])
+
+
 def mlp_fits(widths: list[int]) -> bool:
     """True when a GPU form takes the layer stack: the fused kernels (model in LDS) or the
     streamed-weight form (activations in LDS)."""
-    if not 1 <= len(widths) - 1 <= MLP_MAX_LAYERS:
-        return False
-    fused, stream = mlp_lds_bytes(widths), mlp_stream_lds_bytes(widths)
-    return 0 < fused <= MLP_LDS_BUDGET or 0 < stream <= MLP_LDS_BUDGET
+    return mlp_plan(widths) is not None
 
 
 def _mlp_unflatten(w: torch.Tensor, widths):
@@ -449,7 +469,7 @@ def _mlp_unflatten(w: torch.Tensor, widths):
 
 
 MLP_ACTS = {"relu": 0, "tanh": 1, "sigmoid": 2, "identity": 3}
-MLP_BF16 = 0x100  # flag OR-ed into `act`: bf16 GEMM operands (v_mfma_f32_32x32x16_bf16)
+MLP_BF16 = 0x100  # flag OR-ed into `act`: bf16 GEMM operands (v_mfma_f32_16x16x16_bf16)
 _ACT_FN_BASE = {0: torch.relu, 1: torch.tanh, 2: torch.sigmoid, 3: lambda t: t}
 
 

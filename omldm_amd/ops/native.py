@@ -117,6 +117,8 @@ HIP_SIGS = [
     ("omldm_multiclass_apply", i32, [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp]),
     ("omldm_mlp_lds_bytes", i64, [i32, vp]),
     ("omldm_mlp_stream_lds_bytes", i64, [i32, vp]),
+    ("omldm_mlp_fused16_lds_bytes", i64, [i32, vp]),
+    ("omldm_mlp_plan", i32, [i32, vp, i32, vp]),
     ("omldm_mlp_round", i32, [vp, vp, vp, i64, i32, i32, i32, vp, i32, i32, f32, vp, vp, vp, vp,
                               vp]),
     ("omldm_mlp_forward", i32, [vp, vp, i64, i32, vp, i32, vp, vp]),

@@ -26,7 +26,7 @@ import torch
 from tests.serving_plan_cases import compare
 from tests.serving_plan_nonlinear_cases import reference as nl_reference
 from tests.test_forecast_plans_gpu import (SEVEN, SP, _check, _create, _file_job, _memory_job,
-                                           _moved)
+                                           _moved, _rounds_done)
 from omldm_amd.io.parse import parse_records
 from omldm_amd.io.synthetic import synth_json_records
 
@@ -72,6 +72,7 @@ def test_plans_all_serves_every_learner_publish_update_and_reconfigure(plans_all
             br.produce("trainingData", r)
         for _ in range(4):
             job.tick()
+        _rounds_done(job)
         assert fs.serving and [pid for pid, _, _ in fs._served] == [1, 2, 3, 4, 5, 6, 7]
         assert fs._direct == []
         assert int(fs._plan.table[6, 8 + 0]) == 2, "the tree's PolynomialFeatures: a lazy stage"
@@ -102,6 +103,7 @@ def test_plans_all_serves_every_learner_publish_update_and_reconfigure(plans_all
             br.produce("trainingData", r)
         for _ in range(2):
             job.tick()
+        _rounds_done(job)
         assert not torch.equal(flat0, job.pipes[3].learner.flat)
         assert not torch.equal(tree0, job.pipes[7].learner.state[: tree0.numel()])
         preds = ask(fc)
@@ -156,6 +158,7 @@ def test_plans_all_runs_the_native_lane_with_nn_and_ht(plans_all, tmp_path):
             br.produce("trainingData", r)
         for _ in range(4):
             job.tick()
+        _rounds_done(job)
         assert fs.serving and [pid for pid, _, _ in fs._served] == [1, 2, 3]
         assert not fs._direct
         assert fs.native, "NN and HT plan-served + file topics: the native lane"

@@ -91,6 +91,16 @@ def _three_classes(records):
     return out
 
 
+def _rounds_done(job):
+    """Waits for the ticks' rounds and their publish copy. A tick does not wait for its own
+    round, and the lane adopts a publish only once its copy has completed: until then an
+    answer comes from the bank before it (engine/forecast_server.py, "at most one round
+    stale"), and these tests compare with the model after the last round. As
+    tests/test_forecast_server_gpu.py does after its ticks — on the ticks' stream, not the
+    device: the resident wave runs there."""
+    (job.lanes.compute if job.lanes is not None else torch.cuda.current_stream()).synchronize()
+
+
 def _check(job, pids, fc, preds):
     """Each pipeline's answers, in record order, against its batched predict."""
     batch, _, _ = parse_records(fc, job.space)
@@ -123,6 +133,7 @@ def test_plans_serve_every_kind_publish_and_reconfigure():
             br.produce("trainingData", r)
         for _ in range(4):
             job.tick()
+        _rounds_done(job)
         assert fs.serving and [pid for pid, _, _ in fs._served] == [1, 2, 4, 5, 6]
         assert [pid for pid, _ in fs._direct] == [3, 7]
         assert not fs.native  # in-process topics keep the Python lane
@@ -143,6 +154,7 @@ def test_plans_serve_every_kind_publish_and_reconfigure():
             br.produce("trainingData", r)
         for _ in range(2):
             job.tick()
+        _rounds_done(job)
         n0 = len(preds)
         for r in fc:
             br.produce("forecastingData", r)
@@ -187,6 +199,7 @@ def test_plans_run_the_native_lane_on_file_topics(tmp_path):
             br.produce("trainingData", r)
         for _ in range(4):
             job.tick()
+        _rounds_done(job)
         assert fs.serving and [pid for pid, _, _ in fs._served] == [1, 2, 3]
         assert not fs._direct
         assert fs.native, "every pipeline plan-served + file topics: the native lane"

@@ -339,7 +339,7 @@ def test_hip_mlp_round_vs_reference(cuda, widths, task, act):
 @pytest.mark.parametrize("widths,task,act", [([13, 32, 32, 1], 1, 0), ([40, 64, 48, 5], 2, 1),
                                              ([13, 64, 64, 1], 0, 0)])
 def test_hip_mlp_bf16_matmul_vs_fp32_reference(cuda, widths, task, act):
-    """matmulDtype bf16 (v_mfma_f32_32x32x16_bf16 operands, fp32 accumulate) tracks the
+    """matmulDtype bf16 (v_mfma_f32_16x16x16_bf16 operands, fp32 accumulate) tracks the
     fp32 reference to bf16 rounding; forward output likewise; an exact-integer product
     checks the operand map."""
     B, R, S = 1000, 96, 11
