@@ -62,7 +62,7 @@ inline size_t mcw_lds_bytes(int CR, int FS, int K) {
 }
 
 // Worst-case distinct keys of a spoke of R rows, and the smallest table (log2 entries) at
-// load ≤ 1/2 — ops/dense.py multiclass_wide_table_log2 draws the same line.
+// load ≤ 1/2 — ops/dense.py multiclass_wide_table_log2 asks this function.
 inline int mcw_table_log2(int dn, int dc, int bias, int R, int cspan, int dim) {
   long long range = cspan > 0 ? (long long)dc * cspan : (long long)dim - dn - 1;
   if (range < 0) range = 0;
@@ -486,6 +486,12 @@ using namespace omldm;
 OMLDM_API int omldm_multiclass_wide_fits(int dn, int dc, int bias, int nclass, int R, int cspan,
                                          int dim, int log2gcap) {
   return mcw_fits(dn, dc, bias, nclass, R, cspan, dim, log2gcap) ? 1 : 0;
+}
+
+// log2 of the table entries per spoke the wide round needs for this shape (mcw_table_log2).
+OMLDM_API int omldm_multiclass_wide_table_log2(int dn, int dc, int bias, int R, int cspan,
+                                               int dim) {
+  return mcw_table_log2(dn, dc, bias, R, cspan, dim);
 }
 
 // One Synchronous round of S exact sequential MultiClassPA spokes of R rows on a hashed

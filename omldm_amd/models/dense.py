@@ -8,9 +8,8 @@ slots feed the linear family and MultiClassPA.
 """
 from __future__ import annotations
 
-import os
-
 import math
+from dataclasses import dataclass
 
 import torch
 
@@ -252,17 +251,19 @@ class KMeans(Learner):
 
 
 # ---------------------------------------------------------------------- MultiClassPA
+@dataclass(frozen=True)
+class McRoute:
+    """How one MultiClassPA round runs (``MultiClassPA.route``)."""
+    kind: str  # "dense" | "binary" | "scan" | "wide" | "table"
+    R: int     # rows per spoke
+    S: int     # spokes the kernel is launched with
+
+
 class MultiClassPA(Learner):
     """K-prototype Passive-Aggressive classifier on hashed features (labels 0..K-1);
-    virtual spokes per round. On a GPU: a batch without categorical columns takes the dense
-    round (csrc/kernels/multiclass_dense.hip: the K × (dn + bias) prototypes in LDS, exact
-    sequential spokes, K ≤ 256, fp32 prototypes; ops/dense.py ``multiclass_dense_fits``);
-    the field-aware wire with K ≤ 16 the v3 table scan (csrc/kernels/linear_scan3.hip:
-    s3mc_scan_kernel); a batch with categorical columns and more than 16 classes or more than
-    64 features per row the wide round (csrc/kernels/multiclass_wide.hip: lane = class, the
-    spoke's delta in an HBM table, K ≤ 256, ≤ 256 features, fp32 prototypes; ops/dense.py
-    ``multiclass_wide_fits``); everything else the spoke tables
-    (csrc/kernels/multiclass_spoke.hip)."""
+    virtual spokes per round. Which of the five round forms (dense in LDS, the two-class
+    binary scan, the K-score v3 scan, the wide HBM-table round, the spoke tables) a round
+    takes is decided in one place, ``route``; its docstring holds the table."""
 
     NAME = "MultiClassPA"
     TASK = "classification"
@@ -300,6 +301,42 @@ class MultiClassPA(Learner):
         if self.Wt is not None:
             self.Wt[:, : self.K].copy_(self.W.t())
 
+    def route(self, batch, ctx: RoundContext) -> McRoute:
+        """The kernel this learner's round on ``batch`` takes — what ``fit`` follows. Host
+        queries only (shapes, dtypes, the ``D.MC_*`` switches, the launchers' own limits);
+        first match wins; every kind runs S = ctx.spokes spokes of R = ⌈B/S⌉ rows. exact: the
+        model on a GPU with an fp32 key-major shadow; F = dn + dc + bias; scanfit:
+        ``L.compact_scan_fits`` (compact wire, dc > 0, ≤ 32 fields, dn + bias ≤ 32, R ≤ 8192).
+
+        ====== ==============================================================================
+        kind   condition
+        ====== ==============================================================================
+        dense  exact, ``D.MC_DENSE``, dc = 0, dn ≤ dim − 1, ``D.multiclass_dense_fits``
+               (K ≤ 256, dn + bias ≤ 256, their product ≤ 16384; multiclass_dense.hip)
+        binary exact, K = 2, ``D.MC_BINARY``, scanfit (``_fit_two_classes``)
+        scan   exact, K ≤ ``D._MC_SCAN_KMAX`` (16), scanfit (linear_scan3.hip: s3mc_scan_kernel)
+        wide   exact, ``D.MC_WIDE``, dc > 0, K > 16 or F > 64, ``D.multiclass_wide_fits``
+               (K, F ≤ 256, S tables within ``D.MC_WIDE_BUDGET``; multiclass_wide.hip)
+        table  anything else: CPU, a bf16 shadow, the wide int32 wire inside that box, a shape
+               every other form refuses (multiclass_spoke.hip raises on what it cannot take)
+        ====== =============================================================================="""
+        S = max(1, ctx.spokes)
+        R, dn, dc, K, bias = max(1, -(-batch.B // S)), batch.dn, batch.dc, self.K, self.bias
+        if not (self.W.is_cuda and self.Wt is not None and self.Wt.dtype == torch.float32):
+            return McRoute("table", R, S)
+        if (D.MC_DENSE and dc == 0 and dn <= self.dim - 1
+                and D.multiclass_dense_fits(dn, 0, bias, K)):
+            return McRoute("dense", R, S)
+        scanfit = L.compact_scan_fits(batch, R, bias, self.dim)
+        if scanfit and K == 2 and D.MC_BINARY:
+            return McRoute("binary", R, S)
+        if scanfit and K <= D._MC_SCAN_KMAX:
+            return McRoute("scan", R, S)
+        if (D.MC_WIDE and dc > 0 and (K > 16 or dn + dc + int(bias) > 64)
+                and D.multiclass_wide_fits(dn, dc, bias, K, R, S, batch.cat_span, self.dim)):
+            return McRoute("wide", R, S)
+        return McRoute("table", R, S)
+
     def _fit_two_classes(self, batch, ctx, R: int, S: int) -> bool:
         """Two classes are one binary PA on v = w_0 − w_1: with y' = +1 for class 0 and −1
         for class 1, the margin s_y − s_r is y'·v·x, the hinge loss is the same, the update
@@ -308,10 +345,6 @@ class MultiClassPA(Learner):
         PA: ℓ/‖x‖²). So the round runs the binary v3 scan (its step chain is ~4× shorter
         than the K-score scan's) and the prototypes are rebuilt from v and the invariant
         sum. Same rows, same order, same running totals (hinge loss, margin ≤ 0 mistakes)."""
-        if not (self.W.is_cuda and os.environ.get("OMLDM_MC_BINARY", "1") != "0"
-                and self.Wt is not None and self.Wt.dtype == torch.float32
-                and L.compact_scan_fits(batch, R, self.bias, self.dim)):
-            return False
         yf = batch.y.float()
         yb = torch.where(yf == 0, 1.0, torch.where(yf == 1, -1.0, float("nan")))
         rb = L.compact_raw(batch, batch.dn, yb)
@@ -327,42 +360,27 @@ class MultiClassPA(Learner):
         self.W[0].copy_((ssum + v) * 0.5)
         self.W[1].copy_((ssum - v) * 0.5)
         self.on_state_loaded()  # the key-major shadow
-        return True
+        return True  # (the round took the binary form: it runs only when routed)
 
     def fit(self, batch, ctx):
         if batch.B == 0:
             return
-        S = max(1, ctx.spokes)
-        R = max(1, -(-batch.B // S))
-        dense = (self.W.is_cuda and D.MC_DENSE and batch.dc == 0 and self.Wt is not None
-                 and self.Wt.dtype == torch.float32 and batch.dn <= self.dim - 1
-                 and D.multiclass_dense_fits(batch.dn, batch.dc, self.bias, self.K))
-        if not dense and self.K == 2 and self._fit_two_classes(batch, ctx, R, S):
+        rt = self.route(batch, ctx)
+        if rt.kind == "binary":  # (applies v itself: no multiclass_apply)
+            self._fit_two_classes(batch, ctx, rt.R, rt.S)
             return
-        if dense:
-            # no categorical column: exact sequential spokes on the K × (dn + bias) dense
-            # prototypes in LDS, any K ≤ 256 (K = 2 included)
-            D.multiclass_dense_round(self.W, batch, R, S, self.K, self.variant, self.C,
-                                     self.bias, self.dacc, self.st)
-        elif D.multiclass_scan3_fits(batch, R, self.K, self.bias, self.Wt):
-            # exact sequential spokes on the v3 table scan (K ≤ 16, field-aware wire)
-            D.multiclass_scan3_round(self.Wt, batch, R, S, self.K, self.variant, self.C,
-                                     self.bias, self.dacc, self.st)
-        elif (self.W.is_cuda and D.MC_WIDE and self.Wt is not None
-              and self.Wt.dtype == torch.float32 and batch.dc > 0
-              and (self.K > 16 or batch.dn + batch.dc + int(self.bias) > 64)
-              and D.multiclass_wide_fits(batch.dn, batch.dc, self.bias, self.K, R, S,
-                                         batch.cat_span, self.dim)):
-            # past the scan's and the spoke tables' box (they refuse it): lane = class, the
-            # spoke's delta in an HBM table (K ≤ 256, ≤ 256 features per row)
-            D.multiclass_wide_round(self.W, self.Wt, batch, R, S, self.K, self.variant, self.C,
-                                    self.bias, self.dacc, self.st)
-        else:  # the spoke-table round (LDS delta tables spilling to HBM)
-            D.multiclass_round(self.W, batch, R, S, self.K, self.variant, self.C, self.bias,
-                               self.dacc, self.st, log2cap=hp_int(self.hyper, "tableLog2", 0),
+        rnd = (batch, rt.R, rt.S, self.K, self.variant, self.C, self.bias, self.dacc, self.st)
+        if rt.kind == "dense":
+            D.multiclass_dense_round(self.W, *rnd)
+        elif rt.kind == "scan":
+            D.multiclass_scan3_round(self.Wt, *rnd)
+        elif rt.kind == "wide":
+            D.multiclass_wide_round(self.W, self.Wt, *rnd)
+        else:
+            D.multiclass_round(self.W, *rnd, log2cap=hp_int(self.hyper, "tableLog2", 0),
                                Wt=self.Wt)
         # every spoke with rows is active: ceil(B / R) of them, known on the host
-        D.multiclass_apply(self.W, self.dacc, _host_scalar(self, -(-batch.B // R)), self.Wt,
+        D.multiclass_apply(self.W, self.dacc, _host_scalar(self, -(-batch.B // rt.R)), self.Wt,
                            st=self.st, cum=self.cum, fold=1)
 
     def state_vector(self):

@@ -281,12 +281,8 @@ class LinearLearner(Learner):
         b = self._routed(batch, ctx, rt)
         rb = L.compact_raw(b, self.space.dn)
         self._set_clock()
-        key = L._s3_key(rb, rt.R, rt.S, self.dim, self.rule.bias, self.rule)
-        if isinstance(b.prep, L.Scan3Prep) and b.prep.key == key:
-            return True
-        b.prep = L.linear_scan3_prepare(rb, rt.R, rt.S, self.dim, bool(self.rule.bias),
-                                        self.rule, slot=L._s3_slot_for(key, self.w.device),
-                                        stream=stream, hashed=True)
+        b.prep = L.scan3_prep_for(rb, rt.R, rt.S, self.dim, self.rule, True, self.w.device,
+                                  stream=stream, wait=None)
         return True
 
     @staticmethod

@@ -174,21 +174,16 @@ def multiclass_round(W: torch.Tensor, batch: HashedBatch, R: int, S: int, nclass
 # round-start prototypes and its private delta in LDS (csrc/kernels/multiclass_dense.hip) —
 # exact sequential spokes at any K ≤ 256. OMLDM_MC_DENSE=0 restores the routing without it.
 MC_DENSE = os.environ.get("OMLDM_MC_DENSE", "1") != "0"
-MC_DENSE_MAX_D = 256      # kMcdMaxD
-MC_DENSE_MAX_K = 256      # kMcdMaxK
-MC_DENSE_MAX_KD = 16384   # kMcdMaxKD: w0 + d in 128 KiB of LDS
 # rounds run through the dense kernel in this process (tests)
 MC_DENSE_ROUNDS = 0
 
 
 def multiclass_dense_fits(dn: int, dc: int, bias: bool, nclass: int) -> bool:
-    """The dense MultiClassPA round's shape (omldm_multiclass_dense_fits draws the same
-    line): no categorical column, 1 ≤ D = dn + bias ≤ 256 columns, 2 ≤ K ≤ 256 classes,
-    K·D ≤ 16384."""
-    D_ = int(dn) + int(bool(bias))
-    K = int(nclass)
-    return (int(dc) == 0 and int(dn) >= 0 and 1 <= D_ <= MC_DENSE_MAX_D
-            and 2 <= K <= MC_DENSE_MAX_K and K * D_ <= MC_DENSE_MAX_KD)
+    """The dense MultiClassPA round's shape, as its launcher draws it (host code, no launch:
+    mcd_fits): no categorical column, 1 ≤ D = dn + bias ≤ 256 columns, 2 ≤ K ≤ 256 classes,
+    K·D ≤ 16384 (w0 + d in 128 KiB of LDS)."""
+    return int(dc) == 0 and bool(native.hip().omldm_multiclass_dense_fits(
+        int(dn), int(bool(bias)), int(nclass)))
 
 
 def multiclass_dense_round(W: torch.Tensor, batch: HashedBatch, R: int, S: int, nclass: int,
@@ -232,14 +227,12 @@ def multiclass_dense_round(W: torch.Tensor, batch: HashedBatch, R: int, S: int, 
 
 
 # ------------------------------------------- wide MultiClassPA round (hashed batches, K ≤ 256)
-# Batches with categorical columns past the scan's and the spoke tables' box (K > 16 or more
-# than 64 features per row): one workgroup per spoke, lane = class, the spoke's private delta
-# in an HBM table of class_pad(K) floats per hashed key (csrc/kernels/multiclass_wide.hip).
-# OMLDM_MC_WIDE=0 restores the routing without it.
+# Hashed batches past the scan's and the spoke tables' box: one workgroup per spoke, lane =
+# class, the spoke's private delta in an HBM table of class_pad(K) floats per hashed key
+# (csrc/kernels/multiclass_wide.hip). OMLDM_MC_WIDE=0 restores the routing without it.
 MC_WIDE = os.environ.get("OMLDM_MC_WIDE", "1") != "0"
-MC_WIDE_MAX_F = 256       # kMcwMaxF: features per row (dn + dc + bias)
-MC_WIDE_MAX_K = 256       # kMcwMaxK
-MC_WIDE_MAX_LOG2 = 24     # kMcwMaxLog2: table entries per spoke
+# K = 2 on the compact wire as one binary PA (MultiClassPA._fit_two_classes); 0: the K-score scan
+MC_BINARY = os.environ.get("OMLDM_MC_BINARY", "1") != "0"
 # HBM the tables of one round may take (OMLDM_MC_WIDE_BUDGET_MB, default 16 GiB ≈ 5 % of the
 # card: K = 256 at 16 spokes × 8192 rows with 26 categorical fields takes ≈ 8.6 GB)
 MC_WIDE_BUDGET = int(os.environ.get("OMLDM_MC_WIDE_BUDGET_MB", "16384")) << 20
@@ -250,31 +243,26 @@ _MC_WIDE_WS: dict = {}
 
 
 def multiclass_wide_table_log2(R: int, dn: int, dc: int, bias: bool, cspan: int, dim: int) -> int:
-    """log2 of the wide round's table entries per spoke: the smallest power of two ≥ 2 × the
-    spoke's worst-case distinct keys, dn + bias + min(R·dc, hashed key range); the range is
-    dc·cspan on the compact wire and dim − dn − 1 on the wide one (mcw_table_log2 draws the
-    same line)."""
-    rng = int(dc) * int(cspan) if cspan > 0 else int(dim) - int(dn) - 1
-    distinct = int(dn) + int(bool(bias)) + min(int(R) * int(dc), max(0, rng))
-    return max(0, 2 * distinct - 1).bit_length()
+    """log2 of the wide round's table entries per spoke (the launcher's mcw_table_log2: host
+    code, no launch): the smallest power of two ≥ 2 × the spoke's worst-case distinct keys, dn +
+    bias + min(R·dc, key range); dc·cspan keys on the compact wire, dim − dn − 1 on the wide."""
+    return int(native.hip().omldm_multiclass_wide_table_log2(
+        int(dn), int(dc), int(bool(bias)), int(R), int(cspan), int(dim)))
 
 
 def multiclass_wide_fits(batch_dn: int, batch_dc: int, bias: bool, nclass: int, R: int, S: int,
                          cspan: int, dim: int) -> bool:
-    """The wide MultiClassPA round's shape: 2 ≤ K ≤ 256 classes, 1 ≤ F = dn + dc + bias ≤ 256
-    features per row, and S tables of 2^log2 entries of (2 + class_pad(K)) words (plus the S
-    counters) within the round's HBM budget. omldm_multiclass_wide_fits draws the same line
-    for one table."""
+    """The wide MultiClassPA round's shape: what its launcher takes for one table (mcw_fits:
+    2 ≤ K ≤ 256, 1 ≤ F = dn + dc + bias ≤ 256, at most 2^24 entries), and the S tables of 2^log2
+    entries of (2 + class_pad(K)) words (plus the S counters) within the round's HBM budget."""
     dn, dc, K = int(batch_dn), int(batch_dc), int(nclass)
-    F = dn + dc + int(bool(bias))
-    if not (dn >= 0 and dc >= 0 and 1 <= F <= MC_WIDE_MAX_F and 2 <= K <= MC_WIDE_MAX_K
-            and R >= 1 and S >= 1 and dim >= 1 and cspan >= 0):
+    if R < 1 or S < 1:
         return False
     lg = multiclass_wide_table_log2(R, dn, dc, bias, cspan, dim)
-    if not 1 <= lg <= MC_WIDE_MAX_LOG2:
+    if not native.hip().omldm_multiclass_wide_fits(dn, dc, int(bool(bias)), K, int(R), int(cspan),
+                                                   int(dim), lg):
         return False
-    words = int(S) * (1 << lg) * (2 + class_pad(K)) + int(S)
-    return words * 4 <= MC_WIDE_BUDGET
+    return (int(S) * (1 << lg) * (2 + class_pad(K)) + int(S)) * 4 <= MC_WIDE_BUDGET
 
 
 def multiclass_wide_workspace(device, S: int, log2gcap: int, kp: int,
@@ -598,9 +586,9 @@ _MC_SCAN_KMAX = int(os.environ.get("OMLDM_MC_SCAN_KMAX", "16"))
 
 
 def multiclass_scan3_fits(batch, R: int, nclass: int, bias: bool, Wt) -> bool:
-    """The MultiClassPA round on the v3 table scan (csrc/kernels/linear_scan3.hip,
+    """The MultiClassPA op on the v3 table scan (csrc/kernels/linear_scan3.hip,
     s3mc_scan_kernel) takes this batch: the engine's field-aware wire on a GPU, K ≤ 16 classes,
-    fp32 key-major prototypes, a shape the v3 prep takes."""
+    fp32 key-major prototypes, a v3 prep shape (the learner asks ``MultiClassPA.route``)."""
     from omldm_amd.ops import linear as L
 
     return (Wt is not None and Wt.is_cuda and Wt.dtype == torch.float32 and nclass <= _MC_SCAN_KMAX
@@ -625,14 +613,8 @@ def multiclass_scan3_round(Wt: torch.Tensor, batch, R: int, S: int, nclass: int,
     y = batch.y.float().contiguous() if batch.y.dtype != torch.int8 else batch.y.contiguous()
     rb = L.compact_raw(batch, batch.dn, y)
     rule = L.LinearRule(rule=L.RULE_MULTI, variant=variant, C=C, bias=bias)
-    key = L._s3_key(rb, R, S, dim, bias, rule)
-    sp = getattr(batch, "prep", None)
-    if not (isinstance(sp, L.Scan3Prep) and sp.key == key):
-        sp = L.linear_scan3_prepare(rb, R, S, dim, bias, rule, hashed=True,
-                                    slot=L._s3_slot_for(key, Wt.device))
-        batch.prep = sp
-    elif sp.event is not None:
-        torch.cuda.current_stream(Wt.device).wait_event(sp.event)
+    # (the K-score scan does not read the prep's ready word: it waits on the prep's event)
+    sp = batch.prep = L.scan3_prep_for(rb, R, S, dim, rule, True, Wt.device, wait="event")
     L.SCAN3_ROUNDS += 1
     h = native.hip()
     dev = Wt.device

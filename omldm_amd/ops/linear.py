@@ -458,10 +458,11 @@ def _s3_ready_word(dev, slot):
     return words.data_ptr() + 8 * i, epochs[slot]
 
 
-def _s3_wait_prep(sp, dev) -> None:
+def _s3_wait_prep(sp, dev, word: bool = True) -> None:
     """Order the next v3 launch on the current stream after the prep ``sp`` (an inline prep,
-    or one made when the ready-word table is full, has no ready word: its event)."""
-    if sp.ready is not None:
+    or one made when the ready-word table is full, has no ready word: its event, as always
+    when ``word`` is False: a launch that does not consume the word must not arm it)."""
+    if word and sp.ready is not None:
         _s3_lib().omldm_scan3_wait_next(sp.ready[0], sp.ready[1])
     elif sp.event is not None:
         torch.cuda.current_stream(dev).wait_event(sp.event)
@@ -696,6 +697,22 @@ def linear_scan3_prepare(batch: RawBatch, R: int, S: int, dim: int, bias: bool,
     return Scan3Prep(bufs, ptrs, _s3_key(batch, R, S, dim, bias, rule), ev, slot, ready)
 
 
+def scan3_prep_for(rb: RawBatch, R: int, S: int, dim: int, rule: "LinearRule", hashed: bool,
+                   device, stream=None, wait: str | None = "ready") -> Scan3Prep:
+    """This round's v3 prep: ``rb.prep`` if made for the same key, else a new one into the next
+    ring slot (on ``stream`` if given), left on ``rb.prep`` for the tick's next pipeline. ``wait``
+    orders the current stream after a prep that was found: "ready" by its ready word (the binary
+    launches consume it), "event" on its event (omldm_scan3mc_run never reads the word), or None."""
+    assert wait in ("ready", "event", None), wait
+    key, sp = _s3_key(rb, R, S, dim, rule.bias, rule), rb.prep
+    if not (isinstance(sp, Scan3Prep) and sp.key == key):
+        sp = rb.prep = linear_scan3_prepare(rb, R, S, dim, bool(rule.bias), rule, hashed=hashed,
+                                            slot=_s3_slot_for(key, device), stream=stream)
+    elif wait is not None:
+        _s3_wait_prep(sp, device, word=wait == "ready")
+    return sp
+
+
 def scan3_part_bounds(dim: int, dn: int, dc: int, part: int, parts: int,
                       span: int = 0) -> tuple[int, int]:
     import ctypes
@@ -725,14 +742,7 @@ def linear_scan3_round(w: torch.Tensor, batch: RawBatch, R: int, S: int, dacc: t
     part k with the slice of dacc it completed (its collective may start then)."""
     dim = int(dacc.shape[0]) - 2
     num, y = batch.num, batch.y
-    sp = batch.prep
-    key = _s3_key(batch, R, S, dim, rule.bias, rule)
-    if not (isinstance(sp, Scan3Prep) and sp.key == key):
-        sp = linear_scan3_prepare(batch, R, S, dim, bool(rule.bias), rule, hashed=hashed,
-                                  slot=_s3_slot_for(key, w.device))
-        batch.prep = sp  # the next pipeline of the tick reuses it (same key)
-    else:
-        _s3_wait_prep(sp, w.device)
+    sp = scan3_prep_for(batch, R, S, dim, rule, hashed, w.device)
     global SCAN3_ROUNDS
     SCAN3_ROUNDS += 1
     h = _s3_lib()
@@ -780,13 +790,7 @@ def linear_scan3_round_multi(ws: list, batch: RawBatch, R: int, S: int, daccs: l
     key = _s3_key(batch, R, S, dim, r0.bias, r0)
     assert all(_s3_key(batch, R, S, dim, r.bias, r) == key and r.rule == r0.rule and
                r.variant == r0.variant for r in rules), "pipelines must share the prep and rule"
-    sp = batch.prep
-    if not (isinstance(sp, Scan3Prep) and sp.key == key):
-        sp = linear_scan3_prepare(batch, R, S, dim, bool(r0.bias), r0, hashed=hashed,
-                                  slot=_s3_slot_for(key, ws[0].device))
-        batch.prep = sp
-    else:
-        _s3_wait_prep(sp, ws[0].device)
+    sp = scan3_prep_for(batch, R, S, dim, r0, hashed, ws[0].device)
     global SCAN3_ROUNDS
     SCAN3_ROUNDS += 1
     h = _s3_lib()

@@ -112,6 +112,7 @@ HIP_SIGS = [
     ("omldm_multiclass_dense_round", i32, [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32,
                                            f32, i32, vp, vp, vp, vp]),
     ("omldm_multiclass_wide_fits", i32, [i32, i32, i32, i32, i32, i32, i32, i32]),
+    ("omldm_multiclass_wide_table_log2", i32, [i32, i32, i32, i32, i32, i32]),
     ("omldm_multiclass_wide_round", i32, [vp, i32, vp, i32, i32, vp, i32, i32, vp, i32, i32, i32,
                                           i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, i32, vp]),
     ("omldm_multiclass_apply", i32, [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp]),

@@ -185,3 +185,37 @@ def run_job(field_aware: bool, device, n: int = 1200, ticks: int = 4):
         return out
     finally:
         job.close()
+
+
+# The dense round's shape line written out independently of the launcher (the constants of
+# csrc/kernels/multiclass_dense.hip: kMcdMaxD, kMcdMaxK, kMcdMaxKD = w0 + d in 128 KiB of LDS):
+# the reference ``ops.dense.multiclass_dense_fits`` and the launcher's export are held to.
+MC_DENSE_MAX_D = 256
+MC_DENSE_MAX_K = 256
+MC_DENSE_MAX_KD = 16384
+
+
+def dense_fits_reference(dn: int, dc: int, bias: bool, nclass: int) -> bool:
+    """No categorical column, 1 ≤ D = dn + bias ≤ 256 columns, 2 ≤ K ≤ 256 classes,
+    K·D ≤ 16384."""
+    D_ = int(dn) + int(bool(bias))
+    K = int(nclass)
+    return (int(dc) == 0 and int(dn) >= 0 and 1 <= D_ <= MC_DENSE_MAX_D
+            and 2 <= K <= MC_DENSE_MAX_K and K * D_ <= MC_DENSE_MAX_KD)
+
+
+def check_launcher_draws_the_reference_line() -> None:
+    """omldm_multiclass_dense_fits and ``ops.dense.multiclass_dense_fits`` against the
+    reference over the edges of every bound (host code only: nothing is launched)."""
+    from omldm_amd.ops import dense as D
+    from omldm_amd.ops import native
+
+    h = native.hip()
+    for dn in (0, 1, 5, 63, 64, 127, 252, 255, 256, 300):
+        for bias in (False, True):
+            for K in (1, 2, 3, 16, 17, 64, 65, 128, 256, 257):
+                want = dense_fits_reference(dn, 0, bias, K)
+                assert bool(h.omldm_multiclass_dense_fits(dn, int(bias), K)) == want, (dn, bias, K)
+                assert D.multiclass_dense_fits(dn, 0, bias, K) is want, (dn, bias, K)
+                assert not D.multiclass_dense_fits(dn, 1, bias, K), (dn, bias, K)
+    assert h.omldm_multiclass_dense_ws_words(3, 6, 4) == 4 * (3 * 6 + 8)

@@ -194,3 +194,65 @@ def run_job(field_aware: bool, device, n: int = 1200, ticks: int = 4):
         return out
     finally:
         job.close()
+
+
+# The wide round's shape line written out independently of the launcher (the constants of
+# csrc/kernels/multiclass_wide.hip: kMcwMaxF, kMcwMaxK, kMcwMaxLog2): the reference
+# ``ops.dense.multiclass_wide_table_log2`` / ``multiclass_wide_fits`` and the launcher's
+# exports are held to.
+MC_WIDE_MAX_F = 256       # features per row (dn + dc + bias)
+MC_WIDE_MAX_K = 256
+MC_WIDE_MAX_LOG2 = 24     # table entries per spoke
+
+
+def wide_table_log2_reference(R: int, dn: int, dc: int, bias: bool, cspan: int, dim: int) -> int:
+    """log2 of the wide round's table entries per spoke: the smallest power of two ≥ 2 × the
+    spoke's worst-case distinct keys, dn + bias + min(R·dc, hashed key range); the range is
+    dc·cspan on the compact wire and dim − dn − 1 on the wide one."""
+    rng = int(dc) * int(cspan) if cspan > 0 else int(dim) - int(dn) - 1
+    distinct = int(dn) + int(bool(bias)) + min(int(R) * int(dc), max(0, rng))
+    return max(0, 2 * distinct - 1).bit_length()
+
+
+def wide_fits_reference(batch_dn: int, batch_dc: int, bias: bool, nclass: int, R: int, S: int,
+                        cspan: int, dim: int, budget: int) -> bool:
+    """2 ≤ K ≤ 256 classes, 1 ≤ F = dn + dc + bias ≤ 256 features per row, and S tables of
+    2^log2 entries of (2 + class_pad(K)) words (plus the S counters) within ``budget`` bytes."""
+    from omldm_amd.ops.dense import class_pad
+
+    dn, dc, K = int(batch_dn), int(batch_dc), int(nclass)
+    F = dn + dc + int(bool(bias))
+    if not (dn >= 0 and dc >= 0 and 1 <= F <= MC_WIDE_MAX_F and 2 <= K <= MC_WIDE_MAX_K
+            and R >= 1 and S >= 1 and dim >= 1 and cspan >= 0):
+        return False
+    lg = wide_table_log2_reference(R, dn, dc, bias, cspan, dim)
+    if not 1 <= lg <= MC_WIDE_MAX_LOG2:
+        return False
+    words = int(S) * (1 << lg) * (2 + class_pad(K)) + int(S)
+    return words * 4 <= budget
+
+
+def check_launcher_draws_the_reference_line(monkeypatch) -> None:
+    """omldm_multiclass_wide_fits / _table_log2 and their ``ops.dense`` callers against the
+    reference over the edges of every bound (host code only: nothing is launched)."""
+    from omldm_amd.ops import dense as D
+    from omldm_amd.ops import native
+
+    h = native.hip()
+    monkeypatch.setattr(D, "MC_WIDE_BUDGET", 1 << 62)  # the launcher knows one table, no budget
+    for dn, dc in ((0, 0), (0, 1), (5, 3), (13, 26), (63, 1), (200, 55), (201, 55), (0, 256),
+                   (0, 257), (255, 1)):
+        for bias in (False, True):
+            for K in (1, 2, 16, 17, 256, 257):
+                for R, cspan, dim in ((1, 0, 1 << 10), (300, 10, 1 << 12), (8192, 32767, 1 << 20),
+                                      (1 << 20, 0, 1 << 30), (300, 0, 1 << 8)):
+                    lg = wide_table_log2_reference(R, dn, dc, bias, cspan, dim)
+                    py = wide_fits_reference(dn, dc, bias, K, R, 1, cspan, dim, 1 << 62)
+                    args = (dn, dc, int(bias), K, R, cspan, dim)
+                    assert h.omldm_multiclass_wide_table_log2(dn, dc, int(bias), R, cspan,
+                                                              dim) == lg, (args, lg)
+                    assert D.multiclass_wide_table_log2(R, dn, dc, bias, cspan, dim) == lg, args
+                    assert bool(h.omldm_multiclass_wide_fits(*args, lg)) == py, (args, lg)
+                    assert D.multiclass_wide_fits(dn, dc, bias, K, R, 1, cspan, dim) is py, args
+                    # one entry short of the worst case is refused
+                    assert not h.omldm_multiclass_wide_fits(*args, lg - 1), (args, lg)

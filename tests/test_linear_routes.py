@@ -180,6 +180,36 @@ def test_fit_follows_the_route(kind, cuda, monkeypatch):
     assert float(lrn.dacc[:DIM].abs().sum()) == 0  # applied: the accumulator is clear again
 
 
+@gpu
+def test_multiclass_scan_shares_the_prep_helper(cuda):
+    """The MultiClassPA scan kind finds or makes its prep through the same helper
+    (``L.scan3_prep_for``): a second K = 3 learner on the batch reuses the first one's prep
+    (C is not in the key under PA-I); a PA-II learner, whose 1/(2C) is in the prep's row
+    scale, makes its own."""
+    from omldm_amd.models.dense import MultiClassPA
+
+    space = FeatureSpace(13, 0, 2, DIM, field_aware=True)
+    batch = synth_batch(space, 250, task=2, n_classes=3, seed=7).to(cuda)
+    ctx = RoundContext(spokes=SPOKES, inv_p=1.0 / SPOKES)
+    scan = L.SCAN3_ROUNDS
+    first = MultiClassPA({"nClasses": 3}, space, cuda)
+    assert first.route(batch, ctx).kind == "scan" and batch.prep is None
+    first.fit(batch, ctx)
+    prep = batch.prep
+    assert isinstance(prep, L.Scan3Prep)
+    second = MultiClassPA({"nClasses": 3, "C": 0.5}, space, cuda)
+    second.fit(batch, ctx)
+    assert batch.prep is prep
+    other = MultiClassPA({"nClasses": 3, "variant": "PA-II"}, space, cuda)
+    other.fit(batch, ctx)
+    assert isinstance(batch.prep, L.Scan3Prep) and batch.prep is not prep
+    assert batch.prep.key != prep.key and batch.prep.slot != prep.slot
+    torch.cuda.synchronize()
+    assert L.SCAN3_ROUNDS - scan == 3
+    for lrn in (first, second, other):
+        assert float(lrn.cum[1]) > 0 and bool((lrn.W != 0).any())
+
+
 def idle_round(form, dc, device):
     space, batch = blank(form, 13, dc, False, 0, device)
     lrn = SVM(PLAIN, space, device)

@@ -194,17 +194,13 @@ def test_gpu_multiclass_dense_routing(monkeypatch):
 
 @gpu
 def test_gpu_multiclass_dense_python_and_launcher_draw_the_same_line():
-    """``multiclass_dense_fits`` against omldm_multiclass_dense_fits over the edges of every
-    bound, and the launcher refuses (a negative code, nothing launched) what does not fit."""
+    """omldm_multiclass_dense_fits (and ``multiclass_dense_fits``, which asks it) against the
+    independent reference of tests/multiclass_dense_cases.py over the edges of every bound,
+    and the launcher refuses (a negative code, nothing launched) what does not fit."""
     from omldm_amd.ops import native
 
     h = native.hip()
-    for dn in (0, 1, 5, 63, 64, 127, 252, 255, 256, 300):
-        for bias in (False, True):
-            for K in (1, 2, 3, 16, 17, 64, 65, 128, 256, 257):
-                assert bool(h.omldm_multiclass_dense_fits(dn, int(bias), K)) == \
-                    D.multiclass_dense_fits(dn, 0, bias, K), (dn, bias, K)
-    assert h.omldm_multiclass_dense_ws_words(3, 6, 4) == 4 * (3 * 6 + 8)
+    MC.check_launcher_draws_the_reference_line()
     dev = _cuda()
     W = torch.zeros((65, DIM), device=dev)
     x = torch.zeros((10, 255), device=dev)

@@ -30,6 +30,12 @@ def test_multiclass_dense_fits_extra_edges():
     assert isinstance(D.MC_DENSE_ROUNDS, int) and isinstance(D.MC_DENSE, bool)
 
 
+def test_multiclass_dense_launcher_draws_the_reference_line():
+    """The launcher's shape line (host code of the HIP library: it loads without a device)
+    against the independent reference, over the edges of every bound."""
+    MC.check_launcher_draws_the_reference_line()
+
+
 @pytest.mark.parametrize("shape", MC.SHAPES, ids=MC.shape_id)
 def test_reference_alone_stays_inside_the_caps(shape):
     """The CPU learner against itself with the numerical columns reversed: the two runs

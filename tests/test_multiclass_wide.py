@@ -277,24 +277,14 @@ def test_gpu_multiclass_wide_routing(monkeypatch):
 
 @gpu
 def test_gpu_multiclass_wide_python_and_launcher_draw_the_same_line(monkeypatch):
-    """``multiclass_wide_fits`` against omldm_multiclass_wide_fits over the edges of every
-    bound, and the launcher refuses (a negative code, nothing launched) what does not fit."""
+    """omldm_multiclass_wide_fits / _table_log2 (and ``multiclass_wide_fits`` /
+    ``multiclass_wide_table_log2``, which ask them) against the independent reference of
+    tests/multiclass_wide_cases.py over the edges of every bound, and the launcher refuses (a
+    negative code, nothing launched) what does not fit."""
     from omldm_amd.ops import native
 
     h = native.hip()
-    monkeypatch.setattr(D, "MC_WIDE_BUDGET", 1 << 62)  # the launcher knows one table, no budget
-    for dn, dc in ((0, 0), (0, 1), (5, 3), (13, 26), (63, 1), (200, 55), (201, 55), (0, 256),
-                   (0, 257), (255, 1)):
-        for bias in (False, True):
-            for K in (1, 2, 16, 17, 256, 257):
-                for R, cspan, dim in ((1, 0, 1 << 10), (300, 10, 1 << 12), (8192, 32767, 1 << 20),
-                                      (1 << 20, 0, 1 << 30), (300, 0, 1 << 8)):
-                    lg = D.multiclass_wide_table_log2(R, dn, dc, bias, cspan, dim)
-                    py = D.multiclass_wide_fits(dn, dc, bias, K, R, 1, cspan, dim)
-                    args = (dn, dc, int(bias), K, R, cspan, dim)
-                    assert bool(h.omldm_multiclass_wide_fits(*args, lg)) == py, (args, lg)
-                    # one entry short of the worst case is refused
-                    assert not h.omldm_multiclass_wide_fits(*args, lg - 1), (args, lg)
+    MW.check_launcher_draws_the_reference_line(monkeypatch)
     dev = _cuda()
     dim = 1 << 10
     st = torch.zeros(8, device=dev)

@@ -1,6 +1,6 @@
-"""The wide MultiClassPA round's pure-Python side (ops/dense.py: multiclass_wide_fits,
-multiclass_wide_table_log2) and its oracle, the CPU learner, on the shapes of
-tests/multiclass_wide_cases.py — no GPU."""
+"""The wide MultiClassPA round's host side (ops/dense.py: multiclass_wide_fits,
+multiclass_wide_table_log2, which ask the launcher's host code) and its oracle, the CPU
+learner, on the shapes of tests/multiclass_wide_cases.py — no GPU."""
 import pytest
 import torch
 
@@ -63,6 +63,12 @@ def test_multiclass_wide_fits_budget_edge(monkeypatch):
     assert D.multiclass_wide_table_log2(1 << 20, 13, 26, True, 32767, 1 << 24) == 21
     assert D.multiclass_wide_table_log2(1 << 20, 0, 250, False, 0, 1 << 30) == 29
     assert not D.multiclass_wide_fits(0, 250, False, 20, 1 << 20, 1, 0, 1 << 30)
+
+
+def test_multiclass_wide_launcher_draws_the_reference_line(monkeypatch):
+    """The launcher's shape line and table size (host code of the HIP library: it loads
+    without a device) against the independent reference, over the edges of every bound."""
+    MW.check_launcher_draws_the_reference_line(monkeypatch)
 
 
 @pytest.mark.parametrize("shape", MW.SHAPES, ids=MW.shape_id)

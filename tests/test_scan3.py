@@ -460,7 +460,9 @@ def test_gpu_multiclass_scan3_matches_cpu(K, variant, C, S, R, monkeypatch):
     chunk recurrence, then one scatter of ±τ into the K prototypes; K templates 2 / 4 / 8 /
     16 with the padded classes skipped) against the CPU mirror (dense_cpu.cpp), three rounds
     on the engine's field-aware wire. (K = 2 here with the binary form off.)"""
-    monkeypatch.setenv("OMLDM_MC_BINARY", "0")
+    from omldm_amd.ops import dense as D
+
+    monkeypatch.setattr(D, "MC_BINARY", False)
     _mc_scan3_vs_cpu(K, variant, C, S, R)
 
 
@@ -497,19 +499,21 @@ def test_gpu_multiclass_two_classes_on_the_binary_scan(variant, C, S, R, monkeyp
     """K = 2 as one binary PA on v = w_0 − w_1 at C' = 2C (models/dense.py:
     MultiClassPA._fit_two_classes) against the CPU mirror of the K-prototype rule."""
     from omldm_amd.models.dense import MultiClassPA
+    from omldm_amd.ops import dense as D
 
     taken = []
     orig = MultiClassPA._fit_two_classes
 
-    def spy(self, *a):
-        taken.append(orig(self, *a))
-        return taken[-1]
+    def spy(self, batch, ctx, *a):
+        assert self.route(batch, ctx).kind == "binary"
+        taken.append(self.W.is_cuda)
+        return orig(self, batch, ctx, *a)
 
     monkeypatch.setattr(MultiClassPA, "_fit_two_classes", spy)
-    monkeypatch.delenv("OMLDM_MC_BINARY", raising=False)
+    monkeypatch.setattr(D, "MC_BINARY", True)
     rounds = 3 if R < 8192 else 2
     _mc_scan3_vs_cpu(2, variant, C, S, R, rounds=rounds)
-    assert taken.count(True) == rounds, taken  # every GPU round took the binary form
+    assert taken == [True] * rounds, taken  # every GPU round took the binary form, no CPU one
 
 
 @gpu
