@@ -9,11 +9,27 @@ namespace omldm {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// out[0] += Σ ((x − E)·scale)², out[1] += Σ E²  (n4 = n/4 vectors, tail handled by block 0)
+// The block's sums of a and b added to out[0], out[1] (256 threads, one atomic pair per block).
+__device__ inline void drift_block_add(float a, float b, float* __restrict__ out) {
+  __shared__ float part[8];
+  wave_sum2(a, b);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    part[w] = a;
+    part[4 + w] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicAdd(&out[0], (part[0] + part[1]) + (part[2] + part[3]));
+    atomicAdd(&out[1], (part[4] + part[5]) + (part[6] + part[7]));
+  }
+}
+
+// out[0] += Σ ((x − E)·scale)², out[1] += Σ E²  (n4 = n/4 vectors, tail handled by block 0;
+// x and E 16-byte aligned)
 __global__ __launch_bounds__(256) void drift_norms_kernel(const float* __restrict__ x,
                                                           const float* __restrict__ E, long long n,
                                                           float scale, float* __restrict__ out) {
-  __shared__ float part[8];
   float a = 0.f, b = 0.f;
   const long long n4 = n >> 2;
   const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
@@ -31,17 +47,24 @@ __global__ __launch_bounds__(256) void drift_norms_kernel(const float* __restric
     a += d * d;
     b += E[i] * E[i];
   }
-  wave_sum2(a, b);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    part[w] = a;
-    part[4 + w] = b;
+  drift_block_add(a, b, out);
+}
+
+// The same sums one float per lane: views of x or E that are not 16-byte aligned
+// (a slice that starts inside a flat vector).
+__global__ __launch_bounds__(256) void drift_norms_scalar_kernel(const float* __restrict__ x,
+                                                                 const float* __restrict__ E,
+                                                                 long long n, float scale,
+                                                                 float* __restrict__ out) {
+  float a = 0.f, b = 0.f;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n;
+       i += (long long)gridDim.x * 256) {
+    const float e = E[i];
+    const float d = (x[i] - e) * scale;
+    a += d * d;
+    b += e * e;
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    atomicAdd(&out[0], (part[0] + part[1]) + (part[2] + part[3]));
-    atomicAdd(&out[1], (part[4] + part[5]) + (part[6] + part[7]));
-  }
+  drift_block_add(a, b, out);
 }
 
 // E += alpha·d ; x = E   (full sync: fold the reduced increment, reload the model)
@@ -130,14 +153,17 @@ __device__ inline double fgm_counter(double phi, double phi0, double theta) {
   return fmin(kFgmBig, fmax(0.0, floor(num / theta)));
 }
 
-// GM: msg[0] = 1 when ‖X_i‖² > θ·max(‖E‖², 1) (max-reduced over workers)
+// GM: msg[0] = 1 when ‖X_i‖² > θ·max(‖E‖², 1) (max-reduced over workers); the product is
+// taken in fp32, here and in the Python twin, so both devices decide alike at the boundary
 __global__ void gm_local_kernel(const float* __restrict__ nrm, float thr, double* __restrict__ msg) {
   if (threadIdx.x == 0) msg[0] = nrm[0] > thr * fmaxf(nrm[1], 1.f) ? 1.0 : 0.0;
 }
 
-// FGM worker: φ = ‖X_i‖² − ε‖E‖²; counter increment since the last report; msg = (Δc, φ)
+// FGM worker: φ = ‖X_i‖² − ε‖E‖²; counter increment since the last report; msg = (Δc, φ).
+// The product and the difference round apart, as in the Python twin (no fma contraction).
 __global__ void fgm_local_kernel(const float* __restrict__ nrm, double* __restrict__ st,
                                  double eps, double* __restrict__ msg) {
+#pragma clang fp contract(off)
   if (threadIdx.x != 0) return;
   const double phi = (double)nrm[0] - eps * (double)nrm[1];
   const double c = fgm_counter(phi, st[3], st[2]);
@@ -197,9 +223,12 @@ OMLDM_API int omldm_drift_norms(const float* x, const float* E, long long n, flo
   hipStream_t s = (hipStream_t)stream;
   hipMemsetAsync(out, 0, 2 * sizeof(float), s);
   if (n <= 0) return (int)hipGetLastError();
-  if (((uintptr_t)x | (uintptr_t)E) & 15) return -1;
-  hipLaunchKernelGGL(drift_norms_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, s, x, E, n,
-                     scale, out);
+  if (((uintptr_t)x | (uintptr_t)E) & 15)
+    hipLaunchKernelGGL(drift_norms_scalar_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, E, n,
+                       scale, out);
+  else
+    hipLaunchKernelGGL(drift_norms_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, s, x, E, n,
+                       scale, out);
   return (int)hipGetLastError();
 }
 

@@ -72,13 +72,14 @@ def _fgm_counter(phi: float, phi0: float, theta: float) -> float:
 
 
 def gm_local(nrm: torch.Tensor, thr: float, msg: torch.Tensor) -> None:
-    """msg[0] = 1 if ‖X_i‖² > θ·max(‖E‖², 1) else 0."""
+    """msg[0] = 1 if ‖X_i‖² > θ·max(‖E‖², 1) else 0; the product in fp32, as the kernel's."""
     if nrm.is_cuda:
         check(native.hip().omldm_gm_local(ptr(nrm), float(thr), ptr(msg), native.stream_of(nrm)),
               "omldm_gm_local")
     else:
-        x2, e2 = (float(v) for v in nrm.tolist())
-        msg[0] = 1.0 if x2 > float(torch.tensor(thr, dtype=torch.float32)) * max(e2, 1.0) else 0.0
+        n32 = nrm.detach().float()
+        bound = torch.tensor(thr, dtype=torch.float32) * n32[1].clamp(min=1.0)
+        msg[0] = 1.0 if bool(n32[0] > bound) else 0.0
 
 
 def fgm_local(nrm: torch.Tensor, st: torch.Tensor, eps: float, msg: torch.Tensor) -> None:

@@ -7,6 +7,8 @@ from omldm_amd.ops import native
 from omldm_amd.ops.native import check, ptr
 
 ROWS_PER_BLOCK = 1024
+# per (row block, column) the moment pass leaves f64 Σz, f64 Σz², f32 min, f32 max: 24 bytes
+PARTIAL_FLOATS = 6
 _PART: dict = {}
 
 
@@ -21,7 +23,7 @@ def _partial(device, n: int) -> torch.Tensor:
 def _colstats(x: torch.Tensor, count: float, mean, m2, lo, hi, mode: int) -> None:
     B, d = x.shape
     nblk = -(-B // ROWS_PER_BLOCK)
-    part = _partial(x.device, nblk * d * 4)
+    part = _partial(x.device, nblk * d * PARTIAL_FLOATS)
     rc = native.hip().omldm_colstats_update(ptr(x), B, d, float(count), ptr(mean), ptr(m2),
                                             ptr(lo), ptr(hi), mode, ptr(part), ROWS_PER_BLOCK,
                                             native.stream_of(x))

@@ -60,8 +60,6 @@ def test_gram_cpu_and_orr_solution():
 def test_hip_colstats_scale_poly(cuda):
     torch.manual_seed(0)
     x = torch.randn(5000, 37) * 3 + 5
-    for shift_rows in (1234, 3766):
-        pass
     mean = torch.zeros(37, dtype=torch.float64)
     m2 = torch.zeros_like(mean)
     c = 0.0
