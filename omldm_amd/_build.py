@@ -54,7 +54,9 @@ def _run(cmd: list[str]) -> None:
 
 # per-file extra flags: the k-means chains are issue-bound on one wave, where a packed fp32
 # op costs what two plain ones do plus a wait state per dependent step (no SLP packing)
-FILE_FLAGS = {"kmeans_seq.hip": ["-fno-slp-vectorize"]}
+FILE_FLAGS = {"kmeans_seq.hip": ["-fno-slp-vectorize"],
+              # an fp64 kernel whose one fp32 step is the final cast: no packed fp32 ops
+              "orr_solve.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def hip_sources() -> list[str]:

@@ -41,8 +41,9 @@ class ORR(Learner):
     MFMA pass (csrc/kernels/dense_learners.hip: gram_mfma_kernel) into an fp32 round
     buffer that starts at zero (bounded: one round's rows), folded into the fp64 master
     Gram — the reference keeps Breeze fp64 matrices, and an fp32 running sum of an
-    unbounded stream stops absorbing rows. The solve is a Cholesky factorisation of the
-    (d+1)×(d+1) system, refreshed lazily."""
+    unbounded stream stops absorbing rows. Weights are refreshed lazily; solve: one
+    LDS-resident fp64 Cholesky launch up to d + 1 = 128 (csrc/kernels/orr_solve.hip), while
+    larger systems and the CPU factor the (d+1)×(d+1) system with the library."""
 
     NAME = "ORR"
     TASK = "regression"
@@ -73,6 +74,8 @@ class ORR(Learner):
         self._w = None
 
     def weights(self) -> torch.Tensor:
+        if self._w is None:
+            self._w = D.orr_solve(self.G, self.d, self.lam)
         if self._w is None:
             d = self.d
             A = self.G[: d + 1, : d + 1].double()

@@ -1,7 +1,8 @@
 """Ops of the dense-feature and multi-class learners.
 
-GPU: csrc/kernels/dense_learners.hip (MFMA Gram / K-means assignment) and
-csrc/kernels/multiclass_spoke.hip; CPU: identical math in PyTorch / the C++ mirror.
+GPU: csrc/kernels/dense_learners.hip (MFMA Gram / K-means assignment),
+csrc/kernels/orr_solve.hip (``orr_solve``: the ridge system's fp64 Cholesky solve in one
+launch) and csrc/kernels/multiclass_spoke.hip; CPU: identical math in PyTorch / the C++ mirror.
 """
 from __future__ import annotations
 
@@ -58,6 +59,37 @@ def gram_update(x: torch.Tensor, y: torch.Tensor, G: torch.Tensor,
         cnt += ok.sum()
     z = torch.cat([x[ok], torch.ones((int(ok.sum()), 1)), y[ok].unsqueeze(1)], 1).double()
     G[: d + 2, : d + 2] += (z.T @ z).float()
+
+
+# ------------------------------------------------------------------ ORR solve (d + 1 ≤ 128)
+# The (d + 1)-unknown ridge system of the fp64 Gram, factored and solved in the LDS of one
+# workgroup (csrc/kernels/orr_solve.hip). OMLDM_ORR_SOLVE=0 (or the flag, per process) keeps
+# the library path, which also serves larger systems and the CPU.
+ORR_SOLVE = os.environ.get("OMLDM_ORR_SOLVE", "1") != "0"
+ORR_SOLVE_MAX = 128  # csrc/kernels/orr_solve.hip kOrrMaxN
+# launches of the solve kernel in this process (tests)
+ORR_SOLVES = 0
+
+
+def orr_solve(G: torch.Tensor, d: int, lam: float,
+              out: torch.Tensor | None = None) -> torch.Tensor | None:
+    """fp32 w[d + 1] = (G[:n, :n] + s·I)⁻¹ G[:n, n], n = d + 1, from the fp64 Gram ``G`` of
+    [x, 1, y] (square, row stride ≥ d + 2): s = ``lam`` when it is > 0, else the relative
+    jitter 1e-12·trace/n + 1e-30. One kernel launch on G's stream, written into ``out`` when
+    given. None (nothing launched) when G is not an fp64 GPU tensor, d + 1 > ORR_SOLVE_MAX or
+    the switch is off: the caller then solves with the library."""
+    n = int(d) + 1
+    if not (ORR_SOLVE and G.is_cuda and G.dtype == torch.float64 and 1 <= n <= ORR_SOLVE_MAX):
+        return None
+    assert G.dim() == 2 and G.is_contiguous() and G.shape[0] >= d + 2 and G.shape[1] >= d + 2
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=G.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n
+    global ORR_SOLVES
+    ORR_SOLVES += 1
+    check(native.hip().omldm_orr_solve(ptr(G), G.shape[1], int(d), float(lam), ptr(out),
+                                       native.stream_of(G)), "omldm_orr_solve")
+    return out
 
 
 KMEANS_MAX_BLOCKS = 512  # csrc/kernels/dense_learners.hip kKmeansMaxBlocks
