@@ -10,6 +10,12 @@ the per-block medians (the run-to-run noise a difference has to exceed) and the 
 difference of the two paths' weights.
 
     python bench/orr_solve.py [--out profiles/round8/orr_solve.json]
+
+``--blocked`` runs the same protocol on d ∈ {135, 230, 495, 511}, the sizes of the blocked kernel
+(64 × 64 blocks in an HBM workspace, ⌈n / 64⌉ + 1 launches; default output
+profiles/round9/orr_solve_blocked.json). Each case then also says whether the kernel's median
+beats the library's by more than the larger of the two paths' block-median spreads — the rule
+by which a size is routed to the kernel.
 """
 from __future__ import annotations
 
@@ -29,6 +35,7 @@ from omldm_amd.models.base import RoundContext  # noqa: E402
 from omldm_amd.ops import dense as D  # noqa: E402
 
 DS = (13, 104, 127)
+DS_BLOCKED = (135, 230, 495, 511)
 ROWS = 256
 
 
@@ -73,19 +80,25 @@ def summary(blocks: list[list[float]]) -> dict:
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/round8/orr_solve.json")
+    ap.add_argument("--blocked", action="store_true", help="the blocked kernel's shapes")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--blocks", type=int, default=10)
     ap.add_argument("--block-calls", type=int, default=200)
     a = ap.parse_args(argv)
+    if a.out is None:
+        a.out = ("profiles/round9/orr_solve_blocked.json" if a.blocked
+                 else "profiles/round8/orr_solve.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench/orr_solve.py needs a GPU")
     if a.warmup < 20 or a.blocks * a.block_calls < 2000:
         raise SystemExit("protocol: at least 20 warm-up and 2000 timed calls per path")
     dev = torch.device("cuda", 0)
-    switch = D.ORR_SOLVE
+    switch, route = D.ORR_SOLVE, D.ORR_BLOCKED_ROUTE_MAX
+    if a.blocked:  # every candidate size is measured, whatever weights() routes today
+        D.ORR_BLOCKED_ROUTE_MAX = D.ORR_BLOCKED_MAX
     rows = []
-    for d in DS:
+    for d in DS_BLOCKED if a.blocked else DS:
         L = fitted_learner(d, dev)
         for kernel in (False, True):
             for _ in range(a.warmup):
@@ -101,10 +114,18 @@ def main(argv=None) -> int:
                "torch": summary(blocks[False]), "kernel": summary(blocks[True]),
                "max_weight_diff": diff, "max_abs_weight": wmax}
         row["speedup_median"] = round(row["torch"]["median_us"] / row["kernel"]["median_us"], 2)
+        if a.blocked:
+            spread = max(r["block_median_max_us"] - r["block_median_min_us"]
+                         for r in (row["torch"], row["kernel"]))
+            row["launches"] = (d + 1 + 63) // 64 + 1
+            row["block_medians_us"] = {k: [round(statistics.median(b), 2) for b in blocks[v]]
+                                       for k, v in (("torch", False), ("kernel", True))}
+            row["block_median_spread_us"] = round(spread, 2)
+            row["kernel_wins"] = row["torch"]["median_us"] - row["kernel"]["median_us"] > spread
         rows.append(row)
         print(json.dumps(row), flush=True)
-    D.ORR_SOLVE = switch
-    out = {"bench": "orr_solve", "device": torch.cuda.get_device_name(0), "lambda": 1.0,
+    D.ORR_SOLVE, D.ORR_BLOCKED_ROUTE_MAX = switch, route
+    out = {"bench": "orr_solve_blocked" if a.blocked else "orr_solve", "device": torch.cuda.get_device_name(0), "lambda": 1.0,
            "fit_rows": 2 * ROWS, "warmup_calls_per_path": a.warmup, "blocks": a.blocks,
            "timing": "device events around one stale ORR.weights() call", "cases": rows}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

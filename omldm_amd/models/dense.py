@@ -42,8 +42,10 @@ class ORR(Learner):
     buffer that starts at zero (bounded: one round's rows), folded into the fp64 master
     Gram — the reference keeps Breeze fp64 matrices, and an fp32 running sum of an
     unbounded stream stops absorbing rows. Weights are refreshed lazily; solve: one
-    LDS-resident fp64 Cholesky launch up to d + 1 = 128 (csrc/kernels/orr_solve.hip), while
-    larger systems and the CPU factor the (d+1)×(d+1) system with the library."""
+    LDS-resident fp64 Cholesky launch up to d + 1 = 128, the blocked form of the same kernel
+    (64 × 64 blocks in an HBM workspace, one launch per block column) up to d + 1 =
+    ``ops.dense.ORR_BLOCKED_ROUTE_MAX`` (csrc/kernels/orr_solve.hip), while larger systems and
+    the CPU factor the (d+1)×(d+1) system with the library."""
 
     NAME = "ORR"
     TASK = "regression"
@@ -76,6 +78,8 @@ class ORR(Learner):
     def weights(self) -> torch.Tensor:
         if self._w is None:
             self._w = D.orr_solve(self.G, self.d, self.lam)
+        if self._w is None and self.d + 1 <= D.ORR_BLOCKED_ROUTE_MAX:
+            self._w = D.orr_solve_blocked(self.G, self.d, self.lam)
         if self._w is None:
             d = self.d
             A = self.G[: d + 1, : d + 1].double()

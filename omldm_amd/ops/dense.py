@@ -2,7 +2,8 @@
 
 GPU: csrc/kernels/dense_learners.hip (MFMA Gram / K-means assignment),
 csrc/kernels/orr_solve.hip (``orr_solve``: the ridge system's fp64 Cholesky solve in one
-launch) and csrc/kernels/multiclass_spoke.hip; CPU: identical math in PyTorch / the C++ mirror.
+launch; ``orr_solve_blocked``: the same past 128 unknowns, in 64 × 64 blocks) and
+csrc/kernels/multiclass_spoke.hip; CPU: identical math in PyTorch / the C++ mirror.
 """
 from __future__ import annotations
 
@@ -89,6 +90,47 @@ def orr_solve(G: torch.Tensor, d: int, lam: float,
     ORR_SOLVES += 1
     check(native.hip().omldm_orr_solve(ptr(G), G.shape[1], int(d), float(lam), ptr(out),
                                        native.stream_of(G)), "omldm_orr_solve")
+    return out
+
+
+# ------------------------------------------------------- blocked ORR solve (d + 1 ≤ 512)
+# Past one CU's LDS the factor lives in an HBM workspace, cut into 64 × 64 blocks: one launch per
+# block column and one for the back substitution (csrc/kernels/orr_solve.hip, second half). The
+# sizes PolynomialFeatures(2) makes of 15 to 30 raw features; OMLDM_ORR_SOLVE switches it too.
+ORR_BLOCKED_MAX = 512  # csrc/kernels/orr_solve.hip kOrrBlockedMaxN
+# Largest d + 1 ORR.weights() sends here: the largest measured size at which the kernel's median
+# beats the library's by more than both paths' block-median spreads (profiles/round9/
+# orr_solve_blocked.md). At 512 the kernel's 433 µs is below every library block (≥ 1820 µs),
+# but the library is bimodal there and its own spread exceeds the difference, so the rule holds
+# 512 back.
+ORR_BLOCKED_ROUTE_MAX = 496
+# solves through the blocked kernels in this process (tests)
+ORR_BLOCKED_SOLVES = 0
+
+
+def orr_solve_blocked(G: torch.Tensor, d: int, lam: float,
+                      out: torch.Tensor | None = None) -> torch.Tensor | None:
+    """``orr_solve`` for d + 1 ≤ ORR_BLOCKED_MAX unknowns: the same fp32 w[d + 1] from the same
+    Gram, ⌈(d + 1) / 64⌉ + 1 launches on G's stream, the factor in this stream's ``orr_blocked``
+    workspace. None (nothing launched) when G is not an fp64 GPU tensor, d + 1 >
+    ORR_BLOCKED_MAX or the switch is off."""
+    from omldm_amd.ops.linear import _workspace
+
+    n = int(d) + 1
+    if not (ORR_SOLVE and G.is_cuda and G.dtype == torch.float64 and 1 <= n <= ORR_BLOCKED_MAX):
+        return None
+    assert G.dim() == 2 and G.is_contiguous() and G.shape[0] >= d + 2 and G.shape[1] >= d + 2
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=G.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n
+    h = native.hip()
+    need = int(h.omldm_orr_solve_blocked_ws_bytes(int(d)))
+    work = _workspace(G.device, (need + 3) // 4, key="orr_blocked")
+    global ORR_BLOCKED_SOLVES
+    ORR_BLOCKED_SOLVES += 1
+    check(h.omldm_orr_solve_blocked(ptr(G), G.shape[1], int(d), float(lam), ptr(out), ptr(work),
+                                    work.numel() * 4, native.stream_of(G)),
+          "omldm_orr_solve_blocked")
     return out
 
 
