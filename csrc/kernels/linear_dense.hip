@@ -29,6 +29,7 @@
 //    order into the accumulator — no workgroup waits for another and no float atomics, so
 //    a round is bit-reproducible.
 #include "common.h"
+#include "linear_step.h"
 
 #pragma clang fp contract(off)
 
@@ -36,43 +37,9 @@ namespace omldm {
 namespace {
 
 constexpr int kDenseMax = 256;   // columns (dn + bias) per spoke
-constexpr int kDenseMaxM = 16;   // pipelines per launch
 constexpr int kU = 8;            // rows per unrolled step of the row loop
 constexpr int kStatOff = kDenseMax;      // workspace row: [0, D) deltas, then the statistics
 constexpr int kWsw = kDenseMax + 8;      // loss, n, mistakes, sq_err, σ, overflow, σ·inv_p, -
-
-enum { kHinge = 0, kEps = 1, kLogistic = 2, kPegasos = 3 };
-
-struct DensePipes {
-  const void* w[kDenseMaxM];
-  float C[kDenseMaxM], eps[kDenseMaxM], lr[kDenseMaxM], lam[kDenseMaxM], tbase[kDenseMaxM];
-};
-
-struct DenseOut {
-  float* dacc[kDenseMaxM];
-  double* cum[kDenseMaxM];
-  float* stats[kDenseMaxM];
-};
-
-// v of another lane for the rows of ROWS, v itself for the others.
-template <int CTRL, int ROWS>
-__device__ __forceinline__ float dpp_rows(float v) {
-  const int b = __builtin_bit_cast(int, v);
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(b, b, CTRL, ROWS, 0xF, false));
-}
-
-// Full-wave sum, wave-uniform, in one fixed order: the 16-lane row sums, then row_bcast:15
-// into rows 1 and 3 and row_bcast:31 into rows 2 and 3 leave the total in lane 63 (the
-// rows a step does not write double instead; nothing reads them afterwards).
-__device__ __forceinline__ float wave_sum_last(float v) {
-  v += dpp_mov<0xB1>(v);
-  v += dpp_mov<0x4E>(v);
-  v += dpp_mov<0x124>(v);
-  v += dpp_mov<0x128>(v);
-  v += dpp_rows<0x142, 0xA>(v);
-  v += dpp_rows<0x143, 0xC>(v);
-  return readlane_f(v, 63);
-}
 
 template <int CPL>
 struct DenseShape {
@@ -129,7 +96,6 @@ __global__ __launch_bounds__(64) void dense_round_kernel(
   const int dn = dn_ > 0 ? dn_ : 1;
   const float C = P.C[m], eps = P.eps[m], lr = P.lr[m], lam = P.lam[m], tbase = P.tbase[m];
   const float shr = RULE == kLogistic ? 1.f - lr * lam : 1.f - lam;
-  const float inf = __builtin_inff();
 
   float w0[CPL], d[CPL], fill[CPL];
 #pragma unroll
@@ -171,22 +137,15 @@ __global__ __launch_bounds__(64) void dense_round_kernel(
     // lane i owns row i of the chunk: what the row's step needs besides the model
     const bool skip = yv != yv;  // unlabeled, or past the spoke's last row
     const float ys = skip ? 0.f : yv;
-    float capv = 0.f, denv = 1.f, shv = skip ? 1.f : shr, cyv = 0.f;
+    float pn = 0.f;
     if (RULE == kHinge || RULE == kEps) {
       const float* xrow = xs + (lane < CR ? lane : 0) * ST;
-      float pn = 0.f;
 #pragma unroll 8
       for (int j = 0; j < D; ++j) pn += xrow[j] * xrow[j];
-      if (!skip && pn > 0.f) {
-        capv = variant == 1 ? C : inf;
-        denv = variant == 2 ? pn + 0.5f / C : pn;
-      }
     }
-    if (RULE == kPegasos) {
-      const float T = tbase + (float)(ch * CR + lane);
-      cyv = (1.f / (lam * T)) * ys;
-      shv = skip ? 1.f : (T - 1.f) / T;
-    }
+    float capv, denv, shv, cyv;
+    row_terms<RULE>(skip, ys, pn, tbase + (float)(ch * CR + lane), variant, C, lam, shr, capv,
+                    denv, shv, cyv);
 
     for (int r0 = 0; r0 < nr; r0 += kU) {
 #pragma unroll
@@ -201,19 +160,8 @@ __global__ __launch_bounds__(64) void dense_round_kernel(
         for (int k = 0; k < CPL; ++k) pm = __builtin_fmaf(x[k], w0[k] + d[k], pm);
         const float mg = sigma * wave_sum_last(pm);
         ms[r] = mg;  // every lane stores the same word
-        float c;
-        if (RULE == kPegasos) {
-          c = yt * mg < 1.f ? readlane_f(cyv, r) : 0.f;
-        } else if (RULE == kHinge) {
-          const float loss = fmaxf(0.f, 1.f - yt * mg);
-          c = fminf(readlane_f(capv, r), loss / readlane_f(denv, r)) * yt;
-        } else if (RULE == kEps) {
-          const float err = yt - mg;
-          const float loss = fmaxf(0.f, fabsf(err) - eps);
-          c = fminf(readlane_f(capv, r), loss / readlane_f(denv, r)) * (err >= 0.f ? 1.f : -1.f);
-        } else {
-          c = lr * yt / (1.f + expf(yt * mg));
-        }
+        const float c = step_coef<RULE>(yt, mg, readlane_f(capv, r), readlane_f(denv, r),
+                                        readlane_f(cyv, r), eps, lr);
         float cv = c;
         if (SHR) {
           sigma *= readlane_f(shv, r);
@@ -229,19 +177,7 @@ __global__ __launch_bounds__(64) void dense_round_kernel(
     if (!skip) {
       const float mv = ms[lane];
       nex_l += 1.f;
-      if (RULE == kEps) {
-        const float err = yv - mv;
-        loss_l += fmaxf(0.f, fabsf(err) - eps);
-        sqe_l += err * err;
-      } else if (RULE == kLogistic) {
-        const float z = yv * mv;
-        loss_l += z > 0.f ? log1pf(expf(-z)) : (-z + log1pf(expf(z)));
-        mist_l += z <= 0.f ? 1.f : 0.f;
-      } else {
-        const float ym = yv * mv;
-        loss_l += fmaxf(0.f, 1.f - ym);
-        mist_l += ym <= 0.f ? 1.f : 0.f;
-      }
+      row_stats<RULE>(yv, mv, eps, loss_l, mist_l, sqe_l);
     }
     __syncthreads();
   }
@@ -264,37 +200,6 @@ __global__ __launch_bounds__(64) void dense_round_kernel(
     wrow[kStatOff + 5] = 0.f;
     wrow[kStatOff + 6] = scale;
   }
-}
-
-// The round's fold, one block per pipeline: the S_act workspace rows in spoke order into
-// the accumulator's D touched slots, the round counters, the running totals and the
-// optional per-spoke statistics. The counters are SET (Σσ·inv_p and Σinv_p summed from 0
-// in spoke order): linear_apply leaves them as they are, like every GPU round kernel's.
-__global__ __launch_bounds__(256) void dense_fold_kernel(DenseOut O, const float* __restrict__ ws,
-                                                         int S, int S_act, int dn, int D, int dim,
-                                                         float inv_p) {
-  const int m = blockIdx.x, j = threadIdx.x;
-  const float* wm = ws + (size_t)m * S * kWsw;
-  float* dacc = O.dacc[m];
-  if (j < D) {
-    const int slot = j < dn ? j : dim - 1;
-    float v = dacc[slot];
-    for (int s = 0; s < S_act; ++s) v += wm[(size_t)s * kWsw + j];
-    dacc[slot] = v;
-  }
-  if (j < 8) {
-    float t = 0.f;
-    for (int s = 0; s < S_act; ++s) t += j == 7 ? inv_p : wm[(size_t)s * kWsw + kStatOff + j];
-    if (j == 6) dacc[dim] = t;
-    else if (j == 7) dacc[dim + 1] = t;
-    else if (j != 4 && O.cum[m]) O.cum[m][j] += (double)t;  // σ is no running total
-  }
-  float* st = O.stats[m];
-  if (st)
-    for (int i = j; i < S * 6; i += 256) {
-      const int s = i / 6, c = i - 6 * s;
-      st[i] = s < S_act ? wm[(size_t)s * kWsw + kStatOff + c] : (c == 4 ? 1.f : 0.f);
-    }
 }
 
 template <int CPL, int RULE, bool SHR>
@@ -394,7 +299,7 @@ OMLDM_API int omldm_linear_dense_round(int M, const void* const* w, float* const
     e = dispatch_dense<4>(rule, shr, grid, st, P, num, num_bf16, dn, y, y_i8, B, R, S, dim, ws,
                           variant, bias, w_bf16, inv_p);
   if (e) return e;
-  hipLaunchKernelGGL(dense_fold_kernel, dim3(M), dim3(256), 0, st, O, ws, S, S_act, dn, D, dim,
+  hipLaunchKernelGGL(round_fold_kernel<kWsw>, dim3(M), dim3(256), 0, st, O, ws, S, S_act, dn, D, dim,
                      inv_p);
   return (int)hipGetLastError();
 }

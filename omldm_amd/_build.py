@@ -56,7 +56,9 @@ def _run(cmd: list[str]) -> None:
 # op costs what two plain ones do plus a wait state per dependent step (no SLP packing)
 FILE_FLAGS = {"kmeans_seq.hip": ["-fno-slp-vectorize"],
               # an fp64 kernel whose one fp32 step is the final cast: no packed fp32 ops
-              "orr_solve.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "orr_solve.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # a per-row chain of scalar-valued fp32 steps: nothing to pack
+              "linear_poly.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def hip_sources() -> list[str]:

@@ -238,6 +238,20 @@ class PolyBatch(HashedBatch):
     def _like(self, num, cat, y, raw) -> "PolyBatch":
         return PolyBatch(num, cat, y, raw, self.cat_span, self.pairs)
 
+    def to(self, device, non_blocking: bool = False) -> "PolyBatch":
+        out = super().to(device, non_blocking)
+        out.pairs = None if self.pairs is None else self.pairs.to(device)
+        return out
+
+    def spoke_padded(self, spokes: int) -> "PolyBatch":
+        p = super().spoke_padded(spokes)
+        if isinstance(p, PolyBatch):
+            return p
+        out = self._like(p.num, p.cat, p.y, None)  # (the pairs travel with the padded rows)
+        out.shards = p.shards
+        self._padded = (spokes, out)
+        return out
+
     def expanded(self) -> HashedBatch:
         from omldm_amd.ops.preprocess import poly_expand
 

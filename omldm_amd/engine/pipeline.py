@@ -77,10 +77,11 @@ class Pipeline:
                                       max_msg_params=max_msg_params)
         self.protocol_name = self.protocol.NAME
         # PolynomialFeatures(2) in front of a learner that fuses the map into its update
-        # (ORR): training batches reach the learner unexpanded (api/batch.py: PolyBatch)
+        # (ORR; the linear family at 257-1024 expanded columns on a GPU): training batches
+        # reach the learner unexpanded (api/batch.py: PolyBatch). The learner is asked per
+        # batch (_pre): a linear learner's answer follows its rule, which an Update can change
         last = self.preprocessors[-1] if self.preprocessors else None
         self._fuse_poly2 = (os.environ.get("OMLDM_FUSE_POLY", "1") != "0"  # A/B knob
-                            and getattr(self.learner, "supports_poly2_map", False)
                             and last is not None and last.NAME == "PolynomialFeatures"
                             and last.degree == 2)
         # running statistics (reference Statistics / learning curve, FlinkHub.scala:95-156)
@@ -98,7 +99,7 @@ class Pipeline:
 
     # --------------------------------------------------------------- data path
     def _pre(self, batch: HashedBatch, train: bool) -> HashedBatch:
-        if train and self._fuse_poly2:
+        if train and self._fuse_poly2 and getattr(self.learner, "supports_poly2_map", False):
             for p in self.preprocessors[:-1]:
                 batch = p(batch, train=True)
             pairs = self.preprocessors[-1].pair_index(batch.dn, batch.num.device)

@@ -16,7 +16,8 @@ published Passive-Aggressive family (Crammer et al. 2006) — SURVEY.md Appendix
 * ``LogisticRegression`` (extension, BASELINE.json config 2): SGD on the log loss.
 
 A round is S virtual spokes, each an exact sequential learner on its R-row shard. Which of
-the four round kernels (dense, v3 table scan, v1 / CPU oracle, spoke table) a round takes is
+the five round kernels (dense, fused degree-2, v3 table scan, v1 / CPU oracle, spoke table) a
+round takes is
 decided in one place, ``LinearLearner.route``; its docstring holds the table.
 """
 from __future__ import annotations
@@ -25,7 +26,7 @@ from dataclasses import dataclass
 
 import torch
 
-from omldm_amd.api.batch import FeatureSpace, HashedBatch, RawBatch
+from omldm_amd.api.batch import FeatureSpace, HashedBatch, PolyBatch, RawBatch
 from omldm_amd.models.base import Learner, RoundContext, hp_float, hp_int
 from omldm_amd.ops import linear as L
 
@@ -36,7 +37,7 @@ _VARIANTS = {"PA": L.PA, "PA-I": L.PA1, "PA1": L.PA1, "PA-II": L.PA2, "PA2": L.P
 class Route:
     """How one round runs (``LinearLearner.route``)."""
 
-    kind: str     # "dense" | "scan" | "seq" | "table"
+    kind: str     # "dense" | "poly" | "scan" | "seq" | "table"
     R: int        # rows per spoke
     S: int        # spokes the kernel is launched with
     hashed: bool  # the kernel reads a hashed batch (a raw one is hashed first)
@@ -61,6 +62,25 @@ class LinearLearner(Learner):
         self._rep_valid = False
         self._seq_pending = False
         self._configure()
+
+    @property
+    def supports_poly2_map(self) -> bool:
+        """``fit`` takes an unexpanded ``PolyBatch`` (engine/pipeline.py hands one over only
+        then): a GPU model, a rule of the fused round, and a raw width whose degree-2
+        expansion is the fused round's shape (``L.poly_fits``; scalers in front of the map
+        keep the width)."""
+        return (self.w.is_cuda and L.POLY_ROUND and self.rule.rule in L.V3_RULES
+                and L.poly_fits(self.space.dn, self.space.dc, self.rule.bias))
+
+    def _poly_round(self, batch) -> bool:
+        """``batch`` is a ``PolyBatch`` the fused degree-2 round takes."""
+        r = self.rule
+        if not (isinstance(batch, PolyBatch) and batch.pairs is not None and self.w.is_cuda
+                and L.POLY_ROUND and r.rule in L.V3_RULES and batch.dc == 0):
+            return False
+        cols = batch.dn + int(batch.pairs.shape[0])
+        return (L.poly_fits(batch.dn, 0, r.bias) and cols <= self.dim - 1
+                and cols == batch.dn + batch.dn * (batch.dn + 1) // 2)
 
     def _configure(self) -> None:
         h = self.hyper
@@ -142,6 +162,9 @@ class LinearLearner(Learner):
         ====== ==================================================================== =====
         batch  condition                                                            kind
         ====== ==================================================================== =====
+        poly   gpu, ``L.POLY_ROUND``, dc = 0, the full pair table of dn columns,    poly
+               256 < dn + dn(dn+1)/2 + bias ≤ 1024 columns inside dim − 1
+               (a ``PolyBatch``; linear_poly.hip on the unexpanded rows)
         either gpu, ``L.DENSE_ROUND``, dc = 0, 1 ≤ dn + bias ≤ 256, dn ≤ dim − 1    dense
                (hashed first if raw; linear_dense.hip)
         raw    gpu, v3on, B > 0, ``L.scan3_eligible`` (≤ 32 fields, R ≤ 8192)       scan
@@ -154,7 +177,7 @@ class LinearLearner(Learner):
         either anything else (hashed first if raw; linear_spoke.hip)                table
         ====== ==================================================================== =====
 
-        Hashed batches are spoke-padded first. Dense and table rounds run S = ctx.spokes
+        Hashed batches are spoke-padded first. Dense, poly and table rounds run S = ctx.spokes
         spokes of R = ⌈B/S⌉ rows, idle spokes included; scan and seq rounds only the
         ⌈B/R⌉ spokes with rows (``_geometry``)."""
         r, gpu = self.rule, self.w.is_cuda
@@ -162,6 +185,8 @@ class LinearLearner(Learner):
         if not raw:
             batch = batch.spoke_padded(max(1, int(ctx.spokes)))
         B = batch.B
+        if self._poly_round(batch):
+            return Route("poly", *self._geometry(B, ctx), hashed=True)
         if (gpu and L.DENSE_ROUND and L.dense_fits(batch.dn, batch.dc, r.bias)
                 and batch.dn <= self.dim - 1 and r.rule in L.V3_RULES):
             return Route("dense", *self._geometry(B, ctx), hashed=True)
@@ -178,10 +203,12 @@ class LinearLearner(Learner):
         return Route("table", *self._geometry(B, ctx), hashed=True)
 
     def reduce_parts_apply(self, batch, ctx: RoundContext) -> bool:
-        """The spoke-table round reduces its tables in key-range parts and the dense round
-        reports them after its one launch; the scan and seq rounds complete the accumulator
-        only at their end (no part is final earlier): one reduce and one collective."""
-        return self.supports_reduce_parts and self.route(batch, ctx).kind in ("table", "dense")
+        """The spoke-table round reduces its tables in key-range parts and the dense and
+        fused degree-2 rounds report them after their one launch; the scan and seq rounds
+        complete the accumulator only at their end (no part is final earlier): one reduce
+        and one collective."""
+        kind = self.route(batch, ctx).kind
+        return self.supports_reduce_parts and kind in ("table", "dense", "poly")
 
     def _routed(self, batch, ctx: RoundContext, rt: Route):
         """``batch`` as the routed kernel reads it: hashed if raw, and spoke-padded (a
@@ -231,6 +258,9 @@ class LinearLearner(Learner):
         if rt.kind == "dense":
             L.linear_dense_round(w, batch.contiguous(), R, S, self.dacc, self.rule, ctx.inv_p,
                                  cum=self.cum, parts=parts, on_part=on_part)
+        elif rt.kind == "poly":
+            L.linear_poly_round(w, batch.contiguous(), R, S, self.dacc, self.rule, ctx.inv_p,
+                                cum=self.cum, parts=parts, on_part=on_part)
         elif rt.kind == "table":
             L.linear_round(w, batch, R, S, self.dacc, None, self.rule, ctx.inv_p,
                            self.log2cap, cum=self.cum, ablate=self.ablate, chunk=self.chunk,
@@ -253,13 +283,13 @@ class LinearLearner(Learner):
     # ------------------------------------------------------ several pipelines
     def group_key(self, batch, ctx: RoundContext):
         """Learners whose rounds on ``batch`` can share ONE launch: a key, or None when this
-        one cannot. Dense rounds group by dimension, rule family, variant, bias, shrink mode
+        one cannot. Dense and fused degree-2 rounds group by dimension, rule family, variant, bias, shrink mode
         and model dtype — C, ε, lr, λ and the Pegasos clock may differ, there is no shared
         prep; scan rounds by their v3 prep."""
         kind = self.route(batch, ctx).kind if batch.B > 0 else None
         r = self.rule
-        if kind == "dense":
-            return ("dense", self.dim, r.rule, r.variant, bool(r.bias), L._s3_shrink(r)[0],
+        if kind in ("dense", "poly"):
+            return (kind, self.dim, r.rule, r.variant, bool(r.bias), L._s3_shrink(r)[0],
                     self.w16 is not None)
         if kind != "scan":
             return None
@@ -288,11 +318,11 @@ class LinearLearner(Learner):
     @staticmethod
     def fit_group(learners: list, batch, ctx: RoundContext) -> None:
         """One round of every learner in ``learners`` (equal ``group_key``) on ``batch`` in
-        one launch (ops.linear.linear_scan3_round_multi, or linear_dense_round_multi for a
-        dense round) — each learner ends exactly as its own ``fit`` would leave it."""
+        one launch (ops.linear.linear_scan3_round_multi, or linear_dense_round_multi /
+        linear_poly_round_multi for a dense / fused degree-2 round) — each learner ends exactly as its own ``fit`` would leave it."""
         first = learners[0]
         rt = first.route(batch, ctx)
-        assert rt.kind in ("dense", "scan") and batch.B > 0, rt
+        assert rt.kind in ("dense", "poly", "scan") and batch.B > 0, rt
         batch = first._routed(batch, ctx, rt)
         R, S = rt.R, rt.S
         for lr in learners:
@@ -302,6 +332,9 @@ class LinearLearner(Learner):
         if rt.kind == "dense":
             L.linear_dense_round_multi(ws, batch.contiguous(), R, S, daccs, rules, ctx.inv_p,
                                        cums)
+        elif rt.kind == "poly":
+            L.linear_poly_round_multi(ws, batch.contiguous(), R, S, daccs, rules, ctx.inv_p,
+                                      cums)
         else:
             rb = L.compact_raw(batch, first.space.dn) if rt.hashed else batch
             step = L.scan3_max_pipes()

@@ -1,7 +1,8 @@
 """Linear-family ops: virtual-spoke training round, batched predict, round apply.
 
 GPU tensors → hand-written HIP kernels (csrc/kernels/linear_spoke.hip; batches without
-categorical columns: csrc/kernels/linear_dense.hip).
+categorical columns: csrc/kernels/linear_dense.hip, and behind PolynomialFeatures(2) past
+256 expanded columns csrc/kernels/linear_poly.hip).
 CPU tensors → the C++ reference implementation (csrc/host/linear_cpu.cpp) with the
 identical semantics (golden oracle + CPU engine path).
 """
@@ -318,7 +319,9 @@ def dense_fits(dn: int, dc: int, bias: bool) -> bool:
 
 
 def _dense_launch(ws: list, batch, R: int, S: int, daccs: list, rules: list, inv_p: float,
-                  cums: list, stats: list) -> None:
+                  cums: list, stats: list, poly: bool = False) -> None:
+    """One launch of the dense round, or (``poly``) of the fused degree-2 round on a
+    ``PolyBatch``: the same arguments plus the pair table."""
     import ctypes
 
     M = len(ws)
@@ -326,7 +329,15 @@ def _dense_launch(ws: list, batch, R: int, S: int, daccs: list, rules: list, inv
     dim = int(daccs[0].shape[0]) - 2
     num, y = batch.num, batch.y
     assert 1 <= M <= DENSE_MAX_PIPES and len(daccs) == M and len(rules) == M
-    assert batch.dc == 0 and dense_fits(batch.dn, 0, r0.bias) and batch.dn <= dim - 1
+    if poly:
+        pairs = batch.pairs
+        assert pairs.dtype == torch.int32 and pairs.is_cuda and pairs.is_contiguous()
+        assert pairs.dim() == 2 and pairs.shape[1] == 2
+        cols = batch.dn + int(pairs.shape[0])
+        assert batch.dc == 0 and DENSE_MAX < cols + int(bool(r0.bias)) <= POLY_MAX
+        assert cols <= dim - 1
+    else:
+        assert batch.dc == 0 and dense_fits(batch.dn, 0, r0.bias) and batch.dn <= dim - 1
     assert w0.is_cuda and all(w.dtype == w0.dtype and w.shape[0] == dim and w.is_cuda
                               for w in ws), "one launch: equal dim, every model fp32 or bf16"
     assert w0.dtype in (torch.float32, torch.bfloat16)
@@ -345,10 +356,21 @@ def _dense_launch(ws: list, batch, R: int, S: int, daccs: list, rules: list, inv
     assert r0.rule != RULE_PEGASOS or all(r.lam > 0 and r.tbase >= 2 for r in rules), \
         "Pegasos: λ > 0, T ≥ 2"
     h = native.hip()
-    wsb = _workspace(w0.device, int(h.omldm_linear_dense_ws_words(M, S)), key="dense_ws")
     P = lambda ts: (ctypes.c_void_p * M)(*[ptr(t) for t in ts])  # noqa: E731
     F = lambda vs: (ctypes.c_float * M)(*[float(v) for v in vs])  # noqa: E731
     dp = native.dptr
+    if poly:
+        wsb = _workspace(w0.device, int(h.omldm_linear_poly_ws_words(M, S)), key="poly_ws")
+        check(h.omldm_linear_poly_round(
+            M, P(ws), P(daccs), P(cums), P(stats), F([r.C for r in rules]),
+            F([r.eps for r in rules]), F([r.lr for r in rules]), F([r.lam for r in rules]),
+            F([r.tbase for r in rules]), int(w0.dtype == torch.bfloat16), dp(num),
+            int(num.dtype == torch.bfloat16), batch.dn, ptr(pairs), int(pairs.shape[0]), dp(y),
+            int(y.dtype == torch.int8), batch.B, R, S, dim, ptr(wsb), r0.rule, r0.variant,
+            int(bool(r0.bias)), _s3_shrink(r0)[0], float(inv_p), native.stream_of(w0)),
+            "omldm_linear_poly_round")
+        return
+    wsb = _workspace(w0.device, int(h.omldm_linear_dense_ws_words(M, S)), key="dense_ws")
     check(h.omldm_linear_dense_round(
         M, P(ws), P(daccs), P(cums), P(stats), F([r.C for r in rules]),
         F([r.eps for r in rules]), F([r.lr for r in rules]), F([r.lam for r in rules]),
@@ -398,6 +420,61 @@ def linear_dense_round_multi(ws: list, batch: HashedBatch, R: int, S: int, daccs
         DENSE_MULTI_LAUNCHES += 1
         _dense_launch(ws[i:j], batch, R, S, daccs[i:j], rules[i:j], inv_p, cums[i:j],
                       [None] * len(ws[i:j]))
+
+
+# ------------------------------------------------ fused PolynomialFeatures(2) round (dc = 0)
+# A numerical-only batch behind the degree-2 map whose expansion is 257-1024 columns trains
+# on the unexpanded ``PolyBatch`` (csrc/kernels/linear_poly.hip: the model split over the
+# 2-4 waves of a workgroup, the products formed from the raw row in LDS) — the dense round's
+# semantics, rules and multi-pipeline launch. OMLDM_POLY_ROUND=0 restores the routing
+# without it (A/B): the learner receives the expanded batch.
+POLY_MAX = 1024
+POLY_ROUND = os.environ.get("OMLDM_POLY_ROUND", "1") != "0"
+# rounds / multi-pipeline launches run through the fused kernel in this process (tests)
+POLY_ROUNDS = 0
+POLY_MULTI_LAUNCHES = 0
+
+
+def poly_fits(d0: int, dc: int, bias: bool) -> bool:
+    """The fused round's shape: no categorical column and DENSE_MAX < d0 + d0(d0+1)/2 + bias
+    ≤ POLY_MAX columns (d0 = 22 … 43 with the bias)."""
+    d0 = int(d0)
+    return int(dc) == 0 and DENSE_MAX < d0 + d0 * (d0 + 1) // 2 + int(bool(bias)) <= POLY_MAX
+
+
+def linear_poly_round(w: torch.Tensor, batch, R: int, S: int, dacc: torch.Tensor,
+                      rule: LinearRule, inv_p: float, cum: torch.Tensor | None = None,
+                      stats: torch.Tensor | None = None, parts: int = 1, on_part=None) -> None:
+    """``linear_dense_round`` on ``batch.expanded()`` without making it: one Synchronous
+    round of S exact sequential spokes on a ``PolyBatch`` (GPU; ``poly_fits``). The raw
+    columns accumulate into ``dacc[:dn]``, the products into ``dacc[dn:dn + npairs]``, the
+    bias into ``dacc[dim − 1]``; counters, ``cum``, ``stats`` and ``on_part`` as there."""
+    if S <= 0 or batch.B == 0:
+        return
+    global POLY_ROUNDS
+    POLY_ROUNDS += 1
+    _dense_launch([w], batch, R, S, [dacc], [rule], inv_p, [cum], [stats], poly=True)
+    if on_part is not None:
+        parts = max(1, int(parts))
+        dim = int(dacc.shape[0]) - 2
+        for k in range(parts):
+            on_part(k, *part_bounds(dim, k, parts, cuda=True))
+
+
+def linear_poly_round_multi(ws: list, batch, R: int, S: int, daccs: list, rules: list,
+                            inv_p: float, cums: list | None = None) -> None:
+    """``linear_poly_round`` of M pipelines on ONE batch, ≤ 16 per launch, grouped like
+    ``linear_dense_round_multi``. Each accumulator ends bit-equal to its own round."""
+    if S <= 0 or batch.B == 0:
+        return
+    global POLY_ROUNDS, POLY_MULTI_LAUNCHES
+    cums = cums if cums is not None else [None] * len(ws)
+    for i in range(0, len(ws), DENSE_MAX_PIPES):
+        j = i + DENSE_MAX_PIPES
+        POLY_ROUNDS += 1
+        POLY_MULTI_LAUNCHES += 1
+        _dense_launch(ws[i:j], batch, R, S, daccs[i:j], rules[i:j], inv_p, cums[i:j],
+                      [None] * len(ws[i:j]), poly=True)
 
 
 # GPU kernel of the exact sequential round: "scan3" (linear_scan3.hip, default: LDS slot
