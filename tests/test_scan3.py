@@ -20,6 +20,7 @@ from omldm_amd.io.synthetic import synth_raw
 from omldm_amd.ops import linear as L
 from omldm_amd.ops import native
 from omldm_amd.ops.ingest import hash_raw
+from tests.scan3_ref import _occurrence_flags, _scan3_model
 from tests.test_rawwire import _blocked_gram_scan
 
 gpu = pytest.mark.gpu
@@ -28,132 +29,6 @@ CH = 64
 
 def _cuda():
     return torch.device("cuda", 0)
-
-
-def _occurrence_flags(cat: np.ndarray, a: int, b: int):
-    """The dedupe pass of one spoke (rows [a, b)), per field: for every present occurrence
-    (row, field) → (table id or −1, TG, INIT, SCAT, rank within its chunk's equal slots).
-    TG: the margin reads the table (the slot was first seen in an earlier chunk);
-    INIT: first occurrence of a table slot; SCAT: the slot recurs ≥ 2 chunks later."""
-    out = {}
-    lid = 0
-    for f in range(cat.shape[1]):
-        first, last = {}, {}
-        for t in range(a, b):
-            c = int(cat[t, f])
-            if c == -1:
-                continue
-            s = c & 0x7FFFFFFF
-            first.setdefault(s, t - a)
-            last[s] = t - a
-        ids = {}
-        for s in sorted(first):
-            if (last[s] >> 6) - (first[s] >> 6) >= 2:
-                ids[s] = lid
-                lid += 1
-        seen = {}
-        for t in range(a, b):
-            c = int(cat[t, f])
-            if c == -1:
-                continue
-            s, r = c & 0x7FFFFFFF, t - a
-            tab = s in ids
-            key = (s, r >> 6)
-            rank = seen.get(key, 0)
-            seen[key] = rank + 1
-            out[(t, f)] = (ids.get(s, -1), tab and (r >> 6) > (first[s] >> 6),
-                           tab and r == first[s], tab and (last[s] >> 6) >= (r >> 6) + 2, rank)
-    return out, lid
-
-
-def _scan3_model(w, batch, space, R, S, C=1.0, bias=True):
-    """NumPy model of linear_scan3.hip (PA-I): chunk j's base margin is assembled in the
-    helpers' iteration j − 1 — after chunk j − 2 was scattered into the table — from the
-    table (TG occurrences), w (the rest) and the dense weights after chunks ≤ j − 2; the
-    scanner adds X1_j·c_{j−1} and runs the in-chunk G_j recurrence."""
-    dim = space.dim
-    cat = hash_raw(batch.tok, space).numpy()
-    num = batch.num.double().numpy()
-    y = batch.y.double().numpy()
-    B = batch.B
-    w0 = w.double().numpy()
-    dcols = list(range(space.dn)) + ([dim - 1] if bias else [])
-    acc, n_act = np.zeros(dim), 0
-    for s in range(S):
-        a, b = min(s * R, B), min(s * R + R, B)
-        if a >= b:
-            continue
-        n_act += 1
-        flags, _ = _occurrence_flags(cat, a, b)
-        table = {}
-        wn = w0[dcols].copy()
-        chunks = []
-        for c0 in range(a, b, CH):
-            rows = list(range(c0, min(b, c0 + CH)))
-            X = np.zeros((len(rows), dim))
-            for i, t in enumerate(rows):
-                X[i, :space.dn] = num[t]
-                for f in range(space.dc):
-                    cc = int(cat[t, f])
-                    if cc != -1:
-                        X[i, cc & 0x7FFFFFFF] += -1.0 if cc < 0 else 1.0
-                if bias:
-                    X[i, dim - 1] = 1.0
-            chunks.append((rows, X))
-        cs = []
-        bases = {}
-
-        def build(j):  # helpers' margins of chunk j (iteration j − 1)
-            rows, X = chunks[j]
-            base = X[:, dcols] @ wn
-            for i, t in enumerate(rows):
-                for f in range(space.dc):
-                    cc = int(cat[t, f])
-                    if cc == -1:
-                        continue
-                    lid, tg, init, _, _ = flags[(t, f)]
-                    sl = cc & 0x7FFFFFFF
-                    v = table[lid] if tg else w0[sl]
-                    if init:
-                        table[lid] = w0[sl]
-                    base[i] += -v if cc < 0 else v
-            bases[j] = base
-
-        def scatter(j):  # helpers' scatter of chunk j (iteration j + 1)
-            nonlocal wn
-            rows, X = chunks[j]
-            for i, t in enumerate(rows):
-                for f in range(space.dc):
-                    cc = int(cat[t, f])
-                    if cc == -1:
-                        continue
-                    lid, _, _, sc, _ = flags[(t, f)]
-                    if sc:
-                        table[lid] += -cs[j][i] if cc < 0 else cs[j][i]
-            wn = wn + X[:, dcols].T @ cs[j]
-
-        nch = len(chunks)
-        build(0)
-        for k in range(nch):
-            # iteration k: helpers scatter k − 1, build k + 1; the scanner scans k
-            if k >= 1:
-                scatter(k - 1)
-            if k + 1 < nch:
-                build(k + 1)
-            rows, X = chunks[k]
-            m0 = bases[k].copy()
-            if k >= 1:
-                m0 += (X @ chunks[k - 1][1].T) @ cs[k - 1]
-            G = X @ X.T
-            n2 = (X * X).sum(1)
-            cvec = np.zeros(len(rows))
-            for i, t in enumerate(rows):
-                m = m0[i] + (cvec[:i] * G[i, :i]).sum()
-                cvec[i] = min(C, max(0.0, 1 - y[t] * m) / n2[i]) * y[t]
-            cs.append(cvec)
-        for j, (rows, X) in enumerate(chunks):
-            acc += X.T @ cs[j]
-    return w0 + acc / n_act
 
 
 def test_table_schedule_of_the_v3_scan_is_exact():
