@@ -1068,6 +1068,11 @@ int bucket_geom(int dim, int log2cap, TableGeom* g) {
   if ((g->log2cap - g->log2nb) + g->lgg < 1) return -1;
   return 0;
 }
+
+// linear_wide.hip
+int linear_wide_predict(const void* w, int w_bf16, long long wstride, int M, const void* num,
+                        int num_bf16, int dn, int B, int dim, int bias, const float* wscale,
+                        float* out, hipStream_t st);
 }  // namespace omldm
 
 // 4-byte words of the HBM spill of S spokes (spoke_table.h: Spill), VK floats per entry.
@@ -1146,6 +1151,8 @@ OMLDM_API int omldm_linear_predict(const void* w, int w_bf16, long long wstride,
   if (F <= 64) return dispatch_predict<1>(w, w_bf16, wstride, M, num, num_bf16, dn, cat, dc, B, dim, bias, cspan, wscale, out, st);
   if (F <= 128) return dispatch_predict<2>(w, w_bf16, wstride, M, num, num_bf16, dn, cat, dc, B, dim, bias, cspan, wscale, out, st);
   if (F <= 256) return dispatch_predict<4>(w, w_bf16, wstride, M, num, num_bf16, dn, cat, dc, B, dim, bias, cspan, wscale, out, st);
+  // numerical-only rows up to 2048 columns: a wave strides the row (linear_wide.hip)
+  if (dc == 0) return linear_wide_predict(w, w_bf16, wstride, M, num, num_bf16, dn, B, dim, bias, wscale, out, st);
   return -2;
 }
 

@@ -58,7 +58,9 @@ FILE_FLAGS = {"kmeans_seq.hip": ["-fno-slp-vectorize"],
               # an fp64 kernel whose one fp32 step is the final cast: no packed fp32 ops
               "orr_solve.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               # a per-row chain of scalar-valued fp32 steps: nothing to pack
-              "linear_poly.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "linear_poly.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # the same chain (without the flag the compiler pairs w0 + d and the update fmas)
+              "linear_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def hip_sources() -> list[str]:

@@ -16,8 +16,8 @@ published Passive-Aggressive family (Crammer et al. 2006) — SURVEY.md Appendix
 * ``LogisticRegression`` (extension, BASELINE.json config 2): SGD on the log loss.
 
 A round is S virtual spokes, each an exact sequential learner on its R-row shard. Which of
-the five round kernels (dense, fused degree-2, v3 table scan, v1 / CPU oracle, spoke table) a
-round takes is
+the six round kernels (dense, wide dense, fused degree-2, v3 table scan, v1 / CPU oracle,
+spoke table) a round takes is
 decided in one place, ``LinearLearner.route``; its docstring holds the table.
 """
 from __future__ import annotations
@@ -37,7 +37,7 @@ _VARIANTS = {"PA": L.PA, "PA-I": L.PA1, "PA1": L.PA1, "PA-II": L.PA2, "PA2": L.P
 class Route:
     """How one round runs (``LinearLearner.route``)."""
 
-    kind: str     # "dense" | "poly" | "scan" | "seq" | "table"
+    kind: str     # "dense" | "wide" | "poly" | "scan" | "seq" | "table"
     R: int        # rows per spoke
     S: int        # spokes the kernel is launched with
     hashed: bool  # the kernel reads a hashed batch (a raw one is hashed first)
@@ -167,6 +167,9 @@ class LinearLearner(Learner):
                (a ``PolyBatch``; linear_poly.hip on the unexpanded rows)
         either gpu, ``L.DENSE_ROUND``, dc = 0, 1 ≤ dn + bias ≤ 256, dn ≤ dim − 1    dense
                (hashed first if raw; linear_dense.hip)
+        either gpu, ``L.WIDE_ROUND`` (off by default), dc = 0,                      wide
+               256 < dn + bias ≤ 2048, dn ≤ dim − 1 (hashed first if raw;
+               linear_wide.hip)
         raw    gpu, v3on, B > 0, ``L.scan3_eligible`` (≤ 32 fields, R ≤ 8192)       scan
                (linear_scan3.hip on raw tokens)
         raw    plain (GPU: v1 on [S, dim] replicas, linear_seq.hip, logged once;    seq
@@ -177,7 +180,7 @@ class LinearLearner(Learner):
         either anything else (hashed first if raw; linear_spoke.hip)                table
         ====== ==================================================================== =====
 
-        Hashed batches are spoke-padded first. Dense, poly and table rounds run S = ctx.spokes
+        Hashed batches are spoke-padded first. Dense, wide, poly and table rounds run S = ctx.spokes
         spokes of R = ⌈B/S⌉ rows, idle spokes included; scan and seq rounds only the
         ⌈B/R⌉ spokes with rows (``_geometry``)."""
         r, gpu = self.rule, self.w.is_cuda
@@ -190,6 +193,9 @@ class LinearLearner(Learner):
         if (gpu and L.DENSE_ROUND and L.dense_fits(batch.dn, batch.dc, r.bias)
                 and batch.dn <= self.dim - 1 and r.rule in L.V3_RULES):
             return Route("dense", *self._geometry(B, ctx), hashed=True)
+        if (gpu and L.WIDE_ROUND and L.wide_fits(batch.dn, batch.dc, r.bias)
+                and batch.dn <= self.dim - 1 and r.rule in L.V3_RULES):
+            return Route("wide", *self._geometry(B, ctx), hashed=True)
         R, S = self._geometry(B, ctx, active=True)
         v3on = gpu and L.SEQ_KERNEL == "scan3"
         if raw:
@@ -203,12 +209,12 @@ class LinearLearner(Learner):
         return Route("table", *self._geometry(B, ctx), hashed=True)
 
     def reduce_parts_apply(self, batch, ctx: RoundContext) -> bool:
-        """The spoke-table round reduces its tables in key-range parts and the dense and
+        """The spoke-table round reduces its tables in key-range parts and the dense, wide and
         fused degree-2 rounds report them after their one launch; the scan and seq rounds
         complete the accumulator only at their end (no part is final earlier): one reduce
         and one collective."""
         kind = self.route(batch, ctx).kind
-        return self.supports_reduce_parts and kind in ("table", "dense", "poly")
+        return self.supports_reduce_parts and kind in ("table", "dense", "wide", "poly")
 
     def _routed(self, batch, ctx: RoundContext, rt: Route):
         """``batch`` as the routed kernel reads it: hashed if raw, and spoke-padded (a
@@ -258,6 +264,9 @@ class LinearLearner(Learner):
         if rt.kind == "dense":
             L.linear_dense_round(w, batch.contiguous(), R, S, self.dacc, self.rule, ctx.inv_p,
                                  cum=self.cum, parts=parts, on_part=on_part)
+        elif rt.kind == "wide":
+            L.linear_wide_round(w, batch.contiguous(), R, S, self.dacc, self.rule, ctx.inv_p,
+                                cum=self.cum, parts=parts, on_part=on_part)
         elif rt.kind == "poly":
             L.linear_poly_round(w, batch.contiguous(), R, S, self.dacc, self.rule, ctx.inv_p,
                                 cum=self.cum, parts=parts, on_part=on_part)
@@ -283,12 +292,12 @@ class LinearLearner(Learner):
     # ------------------------------------------------------ several pipelines
     def group_key(self, batch, ctx: RoundContext):
         """Learners whose rounds on ``batch`` can share ONE launch: a key, or None when this
-        one cannot. Dense and fused degree-2 rounds group by dimension, rule family, variant, bias, shrink mode
+        one cannot. Dense, wide and fused degree-2 rounds group by dimension, rule family, variant, bias, shrink mode
         and model dtype — C, ε, lr, λ and the Pegasos clock may differ, there is no shared
         prep; scan rounds by their v3 prep."""
         kind = self.route(batch, ctx).kind if batch.B > 0 else None
         r = self.rule
-        if kind in ("dense", "poly"):
+        if kind in ("dense", "wide", "poly"):
             return (kind, self.dim, r.rule, r.variant, bool(r.bias), L._s3_shrink(r)[0],
                     self.w16 is not None)
         if kind != "scan":
@@ -319,10 +328,11 @@ class LinearLearner(Learner):
     def fit_group(learners: list, batch, ctx: RoundContext) -> None:
         """One round of every learner in ``learners`` (equal ``group_key``) on ``batch`` in
         one launch (ops.linear.linear_scan3_round_multi, or linear_dense_round_multi /
-        linear_poly_round_multi for a dense / fused degree-2 round) — each learner ends exactly as its own ``fit`` would leave it."""
+        linear_wide_round_multi / linear_poly_round_multi for a dense / wide / fused degree-2
+        round) — each learner ends exactly as its own ``fit`` would leave it."""
         first = learners[0]
         rt = first.route(batch, ctx)
-        assert rt.kind in ("dense", "poly", "scan") and batch.B > 0, rt
+        assert rt.kind in ("dense", "wide", "poly", "scan") and batch.B > 0, rt
         batch = first._routed(batch, ctx, rt)
         R, S = rt.R, rt.S
         for lr in learners:
@@ -332,6 +342,9 @@ class LinearLearner(Learner):
         if rt.kind == "dense":
             L.linear_dense_round_multi(ws, batch.contiguous(), R, S, daccs, rules, ctx.inv_p,
                                        cums)
+        elif rt.kind == "wide":
+            L.linear_wide_round_multi(ws, batch.contiguous(), R, S, daccs, rules, ctx.inv_p,
+                                      cums)
         elif rt.kind == "poly":
             L.linear_poly_round_multi(ws, batch.contiguous(), R, S, daccs, rules, ctx.inv_p,
                                       cums)

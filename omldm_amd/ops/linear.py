@@ -1,8 +1,9 @@
 """Linear-family ops: virtual-spoke training round, batched predict, round apply.
 
 GPU tensors → hand-written HIP kernels (csrc/kernels/linear_spoke.hip; batches without
-categorical columns: csrc/kernels/linear_dense.hip, and behind PolynomialFeatures(2) past
-256 expanded columns csrc/kernels/linear_poly.hip).
+categorical columns: csrc/kernels/linear_dense.hip, at 257-2048 columns
+csrc/kernels/linear_wide.hip, and behind PolynomialFeatures(2) past 256 expanded columns
+csrc/kernels/linear_poly.hip).
 CPU tensors → the C++ reference implementation (csrc/host/linear_cpu.cpp) with the
 identical semantics (golden oracle + CPU engine path).
 """
@@ -319,25 +320,30 @@ def dense_fits(dn: int, dc: int, bias: bool) -> bool:
 
 
 def _dense_launch(ws: list, batch, R: int, S: int, daccs: list, rules: list, inv_p: float,
-                  cums: list, stats: list, poly: bool = False) -> None:
-    """One launch of the dense round, or (``poly``) of the fused degree-2 round on a
-    ``PolyBatch``: the same arguments plus the pair table."""
+                  cums: list, stats: list, mode: str = "dense") -> None:
+    """One launch of the register-resident rounds. ``mode``: "dense" (≤ 256 columns), "wide"
+    (257-2048 columns, the same arguments) or "poly" (the fused degree-2 round on a
+    ``PolyBatch``: the same arguments plus the pair table)."""
     import ctypes
 
     M = len(ws)
     r0, w0 = rules[0], ws[0]
     dim = int(daccs[0].shape[0]) - 2
     num, y = batch.num, batch.y
+    assert mode in ("dense", "wide", "poly"), mode
     assert 1 <= M <= DENSE_MAX_PIPES and len(daccs) == M and len(rules) == M
-    if poly:
+    extra = ()
+    if mode == "poly":
         pairs = batch.pairs
         assert pairs.dtype == torch.int32 and pairs.is_cuda and pairs.is_contiguous()
         assert pairs.dim() == 2 and pairs.shape[1] == 2
         cols = batch.dn + int(pairs.shape[0])
         assert batch.dc == 0 and DENSE_MAX < cols + int(bool(r0.bias)) <= POLY_MAX
         assert cols <= dim - 1
+        extra = (ptr(pairs), int(pairs.shape[0]))
     else:
-        assert batch.dc == 0 and dense_fits(batch.dn, 0, r0.bias) and batch.dn <= dim - 1
+        fits = wide_fits if mode == "wide" else dense_fits
+        assert batch.dc == 0 and fits(batch.dn, 0, r0.bias) and batch.dn <= dim - 1
     assert w0.is_cuda and all(w.dtype == w0.dtype and w.shape[0] == dim and w.is_cuda
                               for w in ws), "one launch: equal dim, every model fp32 or bf16"
     assert w0.dtype in (torch.float32, torch.bfloat16)
@@ -359,26 +365,16 @@ def _dense_launch(ws: list, batch, R: int, S: int, daccs: list, rules: list, inv
     P = lambda ts: (ctypes.c_void_p * M)(*[ptr(t) for t in ts])  # noqa: E731
     F = lambda vs: (ctypes.c_float * M)(*[float(v) for v in vs])  # noqa: E731
     dp = native.dptr
-    if poly:
-        wsb = _workspace(w0.device, int(h.omldm_linear_poly_ws_words(M, S)), key="poly_ws")
-        check(h.omldm_linear_poly_round(
-            M, P(ws), P(daccs), P(cums), P(stats), F([r.C for r in rules]),
-            F([r.eps for r in rules]), F([r.lr for r in rules]), F([r.lam for r in rules]),
-            F([r.tbase for r in rules]), int(w0.dtype == torch.bfloat16), dp(num),
-            int(num.dtype == torch.bfloat16), batch.dn, ptr(pairs), int(pairs.shape[0]), dp(y),
-            int(y.dtype == torch.int8), batch.B, R, S, dim, ptr(wsb), r0.rule, r0.variant,
-            int(bool(r0.bias)), _s3_shrink(r0)[0], float(inv_p), native.stream_of(w0)),
-            "omldm_linear_poly_round")
-        return
-    wsb = _workspace(w0.device, int(h.omldm_linear_dense_ws_words(M, S)), key="dense_ws")
-    check(h.omldm_linear_dense_round(
+    name = f"omldm_linear_{mode}"
+    wsb = _workspace(w0.device, int(getattr(h, name + "_ws_words")(M, S)), key=mode + "_ws")
+    check(getattr(h, name + "_round")(
         M, P(ws), P(daccs), P(cums), P(stats), F([r.C for r in rules]),
         F([r.eps for r in rules]), F([r.lr for r in rules]), F([r.lam for r in rules]),
         F([r.tbase for r in rules]), int(w0.dtype == torch.bfloat16),
-        dp(num) if batch.dn else None, int(num.dtype == torch.bfloat16), batch.dn, dp(y),
+        dp(num) if batch.dn else None, int(num.dtype == torch.bfloat16), batch.dn, *extra, dp(y),
         int(y.dtype == torch.int8), batch.B, R, S, dim, ptr(wsb), r0.rule, r0.variant,
         int(bool(r0.bias)), _s3_shrink(r0)[0], float(inv_p), native.stream_of(w0)),
-        "omldm_linear_dense_round")
+        name + "_round")
 
 
 def linear_dense_round(w: torch.Tensor, batch: HashedBatch, R: int, S: int, dacc: torch.Tensor,
@@ -453,7 +449,7 @@ def linear_poly_round(w: torch.Tensor, batch, R: int, S: int, dacc: torch.Tensor
         return
     global POLY_ROUNDS
     POLY_ROUNDS += 1
-    _dense_launch([w], batch, R, S, [dacc], [rule], inv_p, [cum], [stats], poly=True)
+    _dense_launch([w], batch, R, S, [dacc], [rule], inv_p, [cum], [stats], mode="poly")
     if on_part is not None:
         parts = max(1, int(parts))
         dim = int(dacc.shape[0]) - 2
@@ -474,7 +470,58 @@ def linear_poly_round_multi(ws: list, batch, R: int, S: int, daccs: list, rules:
         POLY_ROUNDS += 1
         POLY_MULTI_LAUNCHES += 1
         _dense_launch(ws[i:j], batch, R, S, daccs[i:j], rules[i:j], inv_p, cums[i:j],
-                      [None] * len(ws[i:j]), poly=True)
+                      [None] * len(ws[i:j]), mode="poly")
+
+
+# ------------------------------------------------------------ wide dense round (dc = 0)
+# A numerical-only batch of 257-2048 columns (embeddings, images, sensor channels): the model
+# in the registers of the 2-8 waves of a workgroup, the rows through LDS by chunk
+# (csrc/kernels/linear_wide.hip) — the dense round's semantics, rules and multi-pipeline
+# launch. Off unless OMLDM_WIDE_ROUND=1: without it such a batch routes to the spoke-table
+# round, which refuses it, as before this round existed.
+WIDE_MAX = 2048
+WIDE_ROUND = os.environ.get("OMLDM_WIDE_ROUND", "0") == "1"
+# rounds / multi-pipeline launches run through the wide kernel in this process (tests)
+WIDE_ROUNDS = 0
+WIDE_MULTI_LAUNCHES = 0
+
+
+def wide_fits(dn: int, dc: int, bias: bool) -> bool:
+    """The wide round's shape: no categorical column, DENSE_MAX < dn + bias ≤ WIDE_MAX."""
+    return int(dc) == 0 and DENSE_MAX < int(dn) + int(bool(bias)) <= WIDE_MAX
+
+
+def linear_wide_round(w: torch.Tensor, batch: HashedBatch, R: int, S: int, dacc: torch.Tensor,
+                      rule: LinearRule, inv_p: float, cum: torch.Tensor | None = None,
+                      stats: torch.Tensor | None = None, parts: int = 1, on_part=None) -> None:
+    """``linear_dense_round`` at 257-2048 columns (GPU; ``wide_fits``): the same accumulator,
+    counters, ``cum``, ``stats`` and ``on_part``."""
+    if S <= 0 or batch.B == 0:
+        return
+    global WIDE_ROUNDS
+    WIDE_ROUNDS += 1
+    _dense_launch([w], batch, R, S, [dacc], [rule], inv_p, [cum], [stats], mode="wide")
+    if on_part is not None:
+        parts = max(1, int(parts))
+        dim = int(dacc.shape[0]) - 2
+        for k in range(parts):
+            on_part(k, *part_bounds(dim, k, parts, cuda=True))
+
+
+def linear_wide_round_multi(ws: list, batch: HashedBatch, R: int, S: int, daccs: list,
+                            rules: list, inv_p: float, cums: list | None = None) -> None:
+    """``linear_wide_round`` of M pipelines on ONE batch, ≤ 16 per launch, grouped like
+    ``linear_dense_round_multi``. Each accumulator ends bit-equal to its own round."""
+    if S <= 0 or batch.B == 0:
+        return
+    global WIDE_ROUNDS, WIDE_MULTI_LAUNCHES
+    cums = cums if cums is not None else [None] * len(ws)
+    for i in range(0, len(ws), DENSE_MAX_PIPES):
+        j = i + DENSE_MAX_PIPES
+        WIDE_ROUNDS += 1
+        WIDE_MULTI_LAUNCHES += 1
+        _dense_launch(ws[i:j], batch, R, S, daccs[i:j], rules[i:j], inv_p, cums[i:j],
+                      [None] * len(ws[i:j]), mode="wide")
 
 
 # GPU kernel of the exact sequential round: "scan3" (linear_scan3.hip, default: LDS slot

@@ -64,6 +64,11 @@ HIP_SIGS = [
     ("omldm_linear_poly_round", i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32,
                                       vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32,
                                       f32, vp]),
+    ("omldm_linear_wide_max", i32, []),
+    ("omldm_linear_wide_ws_words", i64, [i32, i32]),
+    ("omldm_linear_wide_round", i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32,
+                                      vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, f32,
+                                      vp]),
     ("omldm_linear_seq_round", i32, [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32,
                                      vp, vp, i32, i32, f32, f32, f32, f32, i32, vp]),
     ("omldm_linear_seq_apply", i32, [vp, vp, i32, vp, i32, vp]),
