@@ -261,15 +261,15 @@ class KMeans(Learner):
 @dataclass(frozen=True)
 class McRoute:
     """How one MultiClassPA round runs (``MultiClassPA.route``)."""
-    kind: str  # "dense" | "binary" | "scan" | "wide" | "table"
+    kind: str  # "dense" | "gram" | "binary" | "scan" | "wide" | "table"
     R: int     # rows per spoke
     S: int     # spokes the kernel is launched with
 
 
 class MultiClassPA(Learner):
     """K-prototype Passive-Aggressive classifier on hashed features (labels 0..K-1);
-    virtual spokes per round. Which of the five round forms (dense in LDS, the two-class
-    binary scan, the K-score v3 scan, the wide HBM-table round, the spoke tables) a round
+    virtual spokes per round. Which of the six round forms (dense in LDS, the chunk-Gram
+    dense round, the two-class binary scan, the K-score v3 scan, the wide HBM-table round, the spoke tables) a round
     takes is decided in one place, ``route``; its docstring holds the table."""
 
     NAME = "MultiClassPA"
@@ -320,6 +320,8 @@ class MultiClassPA(Learner):
         ====== ==============================================================================
         dense  exact, ``D.MC_DENSE``, dc = 0, dn ≤ dim − 1, ``D.multiclass_dense_fits``
                (K ≤ 256, dn + bias ≤ 256, their product ≤ 16384; multiclass_dense.hip)
+        gram   exact, ``D.MC_GRAM`` (off by default), dc = 0, dn ≤ dim − 1,
+               ``D.multiclass_gram_fits`` (K ≤ 256, dn + bias ≤ 2048; multiclass_gram.hip)
         binary exact, K = 2, ``D.MC_BINARY``, scanfit (``_fit_two_classes``)
         scan   exact, K ≤ ``D._MC_SCAN_KMAX`` (16), scanfit (linear_scan3.hip: s3mc_scan_kernel)
         wide   exact, ``D.MC_WIDE``, dc > 0, K > 16 or F > 64, ``D.multiclass_wide_fits``
@@ -334,6 +336,9 @@ class MultiClassPA(Learner):
         if (D.MC_DENSE and dc == 0 and dn <= self.dim - 1
                 and D.multiclass_dense_fits(dn, 0, bias, K)):
             return McRoute("dense", R, S)
+        if (D.MC_GRAM and dc == 0 and dn <= self.dim - 1
+                and D.multiclass_gram_fits(dn, 0, bias, K)):
+            return McRoute("gram", R, S)
         scanfit = L.compact_scan_fits(batch, R, bias, self.dim)
         if scanfit and K == 2 and D.MC_BINARY:
             return McRoute("binary", R, S)
@@ -379,6 +384,8 @@ class MultiClassPA(Learner):
         rnd = (batch, rt.R, rt.S, self.K, self.variant, self.C, self.bias, self.dacc, self.st)
         if rt.kind == "dense":
             D.multiclass_dense_round(self.W, *rnd)
+        elif rt.kind == "gram":
+            D.multiclass_gram_round(self.W, *rnd)
         elif rt.kind == "scan":
             D.multiclass_scan3_round(self.Wt, *rnd)
         elif rt.kind == "wide":

@@ -300,6 +300,64 @@ def multiclass_dense_round(W: torch.Tensor, batch: HashedBatch, R: int, S: int, 
         "omldm_multiclass_dense_round")
 
 
+# ------------------------------------------- chunk-Gram MultiClassPA round (dc = 0, D ≤ 2048)
+# Numerical-only batches past the dense round's box: one workgroup per spoke scores 64-row
+# chunks against w0 + d on the matrix cores and runs the sequential chain on the K scores and
+# the chunk's Gram; w0 and the delta stay in HBM (csrc/kernels/multiclass_gram.hip). Off
+# unless OMLDM_MC_GRAM=1: without it such a batch routes to the spoke-table round, which
+# refuses it, and tests/test_multiclass_routes.py pins that routing.
+MC_GRAM = os.environ.get("OMLDM_MC_GRAM", "0") == "1"
+# rounds run through the chunk-Gram kernel in this process (tests)
+MC_GRAM_ROUNDS = 0
+
+
+def multiclass_gram_fits(dn: int, dc: int, bias: bool, nclass: int) -> bool:
+    """The chunk-Gram MultiClassPA round's shape, as its launcher draws it (host code, no
+    launch: mcg_fits): no categorical column, 1 ≤ D = dn + bias ≤ 2048 columns, 2 ≤ K ≤ 256
+    classes."""
+    return int(dc) == 0 and bool(native.hip().omldm_multiclass_gram_fits(
+        int(dn), int(bool(bias)), int(nclass)))
+
+
+def multiclass_gram_round(W: torch.Tensor, batch: HashedBatch, R: int, S: int, nclass: int,
+                          variant: int, C: float, bias: bool, dacc: torch.Tensor,
+                          stats: torch.Tensor) -> None:
+    """S exact sequential MultiClassPA spokes of R rows on a batch without categorical
+    columns (GPU; ``multiclass_gram_fits``), with the contract of ``multiclass_dense_round``:
+    dacc[K, dim] += Σ_s Δ_s (only its columns [0, dn) and dim − 1 are written), stats[0..3]
+    += (loss, rows, mistakes, spokes with rows). One round launch and one fold launch, no
+    atomics: the same inputs give the same bits."""
+    from omldm_amd.ops.linear import _workspace
+
+    if S <= 0 or batch.B == 0:
+        return
+    K, dim = W.shape
+    num, y = batch.num, batch.y
+    dn = int(batch.dn)
+    assert K == nclass and batch.dc == 0 and multiclass_gram_fits(dn, 0, bias, nclass)
+    assert dn <= dim - 1
+    assert W.is_cuda and W.dtype == torch.float32 and W.is_contiguous()
+    assert dacc.is_cuda and dacc.dtype == torch.float32 and dacc.is_contiguous()
+    assert dacc.shape == W.shape
+    assert stats.is_cuda and stats.dtype == torch.float32 and stats.numel() >= 6
+    assert num.dtype in (torch.float32, torch.bfloat16) and y.dtype in (torch.float32, torch.int8)
+    assert num.is_contiguous() and y.is_contiguous() and int(num.shape[1]) == dn
+    assert all(t.is_cuda or t.is_pinned() for t in ((num, y) if dn else (y,)))
+    assert variant in (0, 1, 2) and C > 0
+    global MC_GRAM_ROUNDS
+    MC_GRAM_ROUNDS += 1
+    h = native.hip()
+    D_ = dn + int(bool(bias))
+    ws = _workspace(W.device, int(h.omldm_multiclass_gram_ws_words(nclass, D_, S)),
+                    key="mc_gram_ws")
+    dp = native.dptr
+    check(h.omldm_multiclass_gram_round(
+        ptr(W), dp(num) if dn else None, int(num.dtype == torch.bfloat16), dn, dp(y),
+        int(y.dtype == torch.int8), batch.B, R, S, dim, nclass, int(variant), float(C),
+        int(bool(bias)), ptr(dacc), ptr(stats), ptr(ws), native.stream_of(W)),
+        "omldm_multiclass_gram_round")
+
+
 # ------------------------------------------- wide MultiClassPA round (hashed batches, K ≤ 256)
 # Hashed batches past the scan's and the spoke tables' box: one workgroup per spoke, lane =
 # class, the spoke's private delta in an HBM table of class_pad(K) floats per hashed key

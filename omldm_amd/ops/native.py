@@ -124,6 +124,10 @@ HIP_SIGS = [
     ("omldm_multiclass_dense_ws_words", i64, [i32, i32, i32]),
     ("omldm_multiclass_dense_round", i32, [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32,
                                            f32, i32, vp, vp, vp, vp]),
+    ("omldm_multiclass_gram_fits", i32, [i32, i32, i32]),
+    ("omldm_multiclass_gram_ws_words", i64, [i32, i32, i32]),
+    ("omldm_multiclass_gram_round", i32, [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32,
+                                          f32, i32, vp, vp, vp, vp]),
     ("omldm_multiclass_wide_fits", i32, [i32, i32, i32, i32, i32, i32, i32, i32]),
     ("omldm_multiclass_wide_table_log2", i32, [i32, i32, i32, i32, i32, i32]),
     ("omldm_multiclass_wide_round", i32, [vp, i32, vp, i32, i32, vp, i32, i32, vp, i32, i32, i32,
