@@ -7,6 +7,10 @@
 // on the fp32-input matrix cores (v_mfma_f32_32x32x2_f32: exact fp32, one rounding per
 // product — the normal equations need it), split over row-chunks across workgroups and
 // combined with row-contiguous f32 atomics (256-B rows: full-rate atomics).
+// Three kernels share the work by width dz = d + 2: gram_map_kernel (below) up to 128 columns,
+// orr_gram.hip from 129 to 1024, and gram_mfma_kernel, the oldest, for wider rows, for a
+// fused map of more than 61 raw features, and behind the OMLDM_GRAM_V1 / OMLDM_GRAM_WIDE=0
+// A/B switches.
 //
 // K-means (online / sequential k-means, single-learner mode): assignment by nearest
 // centroid and per-cluster sums; the centroid move c ← c + (Σx − m·c)/(n + m) is the
@@ -781,7 +785,8 @@ OMLDM_API int omldm_kmeans_assign(const float* x, const float* y, int B, int d, 
 
 // G += Σ zzᵀ with z = [x, x_a·x_b for (a, b) in pairs, 1, y] over rows with finite y: the
 // Gram of PolynomialFeatures(2)(x) without materialising the expansion (pairs: int32
-// [npairs][2]; d0 + npairs + 2 ≤ 128, else -2: expand and call omldm_gram_update).
+// [npairs][2]; d0 + npairs + 2 ≤ 128, else -2: omldm_gram_update_wide of orr_gram.hip takes 129
+// to 1024 columns; past that, expand and call omldm_gram_update).
 OMLDM_API int omldm_gram_update_poly2(const float* x, const float* y, int B, int d0,
                                       const int* pairs, int npairs, float* G, int ld, double* cnt,
                                       float* part, void* stream) {

@@ -38,7 +38,9 @@ class ORR(Learner):
     """Online ridge regression: A = λI + Σxxᵀ, b = Σyx, w = A⁻¹b (intercept included).
     State = the augmented Gram matrix of [x, 1, y] — additive sufficient statistics, so
     worker merges are sums (merge_mode "sum") and exact. The per-round update is one
-    MFMA pass (csrc/kernels/dense_learners.hip: gram_mfma_kernel) into an fp32 round
+    MFMA pass (csrc/kernels/dense_learners.hip: gram_map_kernel up to d + 2 = 128 columns;
+    csrc/kernels/orr_gram.hip from 129 to ``ops.dense.GRAM_WIDE_MAX`` = 1024, the
+    PolynomialFeatures(2) map fused in both; gram_mfma_kernel past that) into an fp32 round
     buffer that starts at zero (bounded: one round's rows), folded into the fp64 master
     Gram — the reference keeps Breeze fp64 matrices, and an fp32 running sum of an
     unbounded stream stops absorbing rows. Weights are refreshed lazily; solve: one

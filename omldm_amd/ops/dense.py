@@ -24,6 +24,35 @@ def _gram_part(device) -> torch.Tensor:
     return _workspace(device, 256 * 10 * 1024, key="gram_part")
 
 
+# ------------------------------------------------------- wide Gram round (129 ≤ d + 2 ≤ 1024)
+# Past the 128 columns of gram_map_kernel: upper-triangle 128 × 128 macro-tiles, one 64 × 64
+# quadrant per wave, LDS-staged 64-row chunks, the PolynomialFeatures(2) map fused into the
+# operand fetch, and a fixed-order reduction instead of atomics (csrc/kernels/orr_gram.hip).
+# OMLDM_GRAM_WIDE=0 (or the flag, per process) restores the routing without it.
+GRAM_WIDE = os.environ.get("OMLDM_GRAM_WIDE", "1") != "0"
+GRAM_WIDE_MIN = 129   # csrc/kernels/orr_gram.hip kGwMinDz
+GRAM_WIDE_MAX = 1024  # csrc/kernels/orr_gram.hip kGwMaxDz
+GRAM_WIDE_MAP_D0 = 61  # raw features of a fused map (kGwMapD0: the staged raw row ≤ 64 columns)
+# rounds through the wide kernel in this process (tests)
+GRAM_WIDE_UPDATES = 0
+
+
+def _gram_update_wide(x, y, G, cnt, pairs) -> None:
+    from omldm_amd.ops.linear import _workspace
+
+    B, d0 = x.shape
+    npairs = 0 if pairs is None else int(pairs.shape[0])
+    assert G.is_cuda and G.dtype == torch.float32 and G.dim() == 2 and G.is_contiguous()
+    h = native.hip()
+    need = int(h.omldm_gram_wide_ws_bytes(B, d0 + npairs + 2))
+    work = _workspace(x.device, (need + 3) // 4, key="gram_wide")
+    global GRAM_WIDE_UPDATES
+    GRAM_WIDE_UPDATES += 1
+    check(h.omldm_gram_update_wide(ptr(x), ptr(y), B, d0, ptr(pairs), npairs, ptr(G), G.shape[1],
+                                   ptr(cnt), ptr(work), work.numel() * 4, native.stream_of(x)),
+          "omldm_gram_update_wide")
+
+
 def gram_update(x: torch.Tensor, y: torch.Tensor, G: torch.Tensor,
                 cnt: torch.Tensor | None = None, pairs: torch.Tensor | None = None) -> None:
     """G[:d+2, :d+2] += Σ_rows z zᵀ with z = [x, 1, y] over rows whose y is finite;
@@ -31,7 +60,10 @@ def gram_update(x: torch.Tensor, y: torch.Tensor, G: torch.Tensor,
     the Gram's (d, d) entry inside the same kernel. ``pairs`` (int32 [np, 2]): x holds the
     raw features of a PolynomialFeatures(2) map and z = [x, x_a·x_b per pair, 1, y] — the
     GPU kernel forms the products in its operand fetch (csrc/kernels/dense_learners.hip
-    gram_map_kernel), so the expansion never reaches HBM."""
+    gram_map_kernel up to d + 2 = 128, csrc/kernels/orr_gram.hip from 129 to GRAM_WIDE_MAX), so
+    the expansion never reaches HBM. On the GPU the wide kernel also takes the plain form at
+    those widths; wider rows, or the switch set off, go to gram_mfma_kernel (a map expanded
+    first)."""
     B, d0 = x.shape
     if B == 0:
         return
@@ -41,6 +73,12 @@ def gram_update(x: torch.Tensor, y: torch.Tensor, G: torch.Tensor,
     if pairs is not None:
         pairs = pairs.to(device=x.device, dtype=torch.int32).contiguous()
         assert pairs.dim() == 2 and pairs.shape[1] == 2
+    dz = d0 + (0 if pairs is None else pairs.shape[0]) + 2
+    if (x.is_cuda and GRAM_WIDE and GRAM_WIDE_MIN <= dz <= GRAM_WIDE_MAX
+            and (pairs is None or d0 <= GRAM_WIDE_MAP_D0)):
+        _gram_update_wide(x, y, G, cnt, pairs)
+        return
+    if pairs is not None:
         if x.is_cuda and d0 + pairs.shape[0] + 2 <= 128:
             check(native.hip().omldm_gram_update_poly2(
                 ptr(x), ptr(y), B, d0, ptr(pairs), pairs.shape[0], ptr(G), G.shape[1], ptr(cnt),

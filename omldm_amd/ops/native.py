@@ -113,6 +113,8 @@ HIP_SIGS = [
     ("omldm_h2d_async", i32, [vp, vp, i64, vp]),
     ("omldm_gram_update", i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp]),
     ("omldm_gram_update_poly2", i32, [vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp]),
+    ("omldm_gram_wide_ws_bytes", i64, [i32, i32]),
+    ("omldm_gram_update_wide", i32, [vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, i64, vp]),
     ("omldm_orr_solve", i32, [vp, i32, i32, f64, vp, vp]),
     ("omldm_orr_solve_blocked_ws_bytes", i64, [i32]),
     ("omldm_orr_solve_blocked", i32, [vp, i32, i32, f64, vp, vp, i64, vp]),
