@@ -723,13 +723,18 @@ static int kmeans_colsum(const float* bpart, int nb, int k, int d, float* sums, 
   return (int)hipGetLastError();
 }
 
-// bpart (optional, with sums): a [kKmeansMaxBlocks][k·d + k + 1] float scratch image for
-// the per-block partials (see kmeans_flush); nullptr: per-block atomics.
-OMLDM_API int omldm_kmeans_assign(const float* x, const float* y, int B, int d, int k,
-                                  const float* cent, float* sums, float* counts, int* assign,
-                                  float* inertia, float* bpart, void* stream) {
-  if (B <= 0) return 0;
-  if (!sums) bpart = nullptr;
+// The LDS rule of omldm_kmeans_assign, in one place: which kernel takes (d, k) and with how many
+// bytes. Both kernels keep every centroid and the k × d cluster sums in one workgroup's LDS.
+struct KmeansFit {
+  bool mfma;   // kmeans_assign_mfma_kernel<dm>, else kmeans_assign_kernel<dm>
+  int dm;      // the kernel's DMAX
+  size_t lds;  // dynamic LDS bytes; 0: neither kernel fits
+};
+
+static KmeansFit kmeans_assign_fit(int d, int k) {
+  constexpr size_t kCap = 150 * 1024;
+  KmeansFit f{false, 0, 0};
+  if (d < 1 || k < 1 || (long long)k * d > (long long)(kCap / 4)) return f;
   // matrix-core distances once there is a full 32-centroid tile and a few features
   // (OMLDM_KMEANS_MFMA=0: the scalar kernel, A/B)
   const char* mf = getenv("OMLDM_KMEANS_MFMA");
@@ -741,31 +746,49 @@ OMLDM_API int omldm_kmeans_assign(const float* x, const float* y, int B, int d, 
                  : da <= 96 ? 96 : 128;
     const int kp = (k + 31) & ~31, ldc = dm | 1;
     const size_t lds = ((size_t)kp * ldc + (size_t)k * d + k) * 4;
-    if (lds <= 150 * 1024) {
-      hipStream_t st = (hipStream_t)stream;
-      int nb = 0, rc = -2;
+    if (lds <= kCap) return KmeansFit{true, dm, lds};
+  }
+  const int dm = d <= 16 ? 16 : d <= 32 ? 32 : d <= 64 ? 64 : 0;
+  const size_t lds = ((size_t)k * (dm ? dm : d) + (size_t)k * d + k) * 4;
+  if (lds <= kCap) f = KmeansFit{false, dm, lds};
+  return f;
+}
+
+// 1 when one of omldm_kmeans_assign's kernels holds k centroids of d features (and their sums)
+// in one workgroup's LDS; 0: omldm_kmeans_assign returns −1 (kmeans_wide.hip takes such shapes).
+OMLDM_API int omldm_kmeans_assign_fits(int d, int k) { return kmeans_assign_fit(d, k).lds != 0; }
+
+// bpart (optional, with sums): a [kKmeansMaxBlocks][k·d + k + 1] float scratch image for
+// the per-block partials (see kmeans_flush); nullptr: per-block atomics.
+OMLDM_API int omldm_kmeans_assign(const float* x, const float* y, int B, int d, int k,
+                                  const float* cent, float* sums, float* counts, int* assign,
+                                  float* inertia, float* bpart, void* stream) {
+  if (B <= 0) return 0;
+  if (!sums) bpart = nullptr;
+  const KmeansFit fit = kmeans_assign_fit(d, k);
+  if (!fit.lds) return -1;
+  const int dm = fit.dm;
+  const size_t lds = fit.lds;
+  hipStream_t st = (hipStream_t)stream;
+  if (fit.mfma) {
+    int nb = 0, rc = -2;
 #define OMLDM_KMM(DM)                                                                           \
   if (dm == DM)                                                                                 \
   rc = launch_kmeans_mfma<DM>(x, y, B, d, k, cent, sums, counts, assign, inertia, bpart, lds, st, \
                               &nb)
-      OMLDM_KMM(16);
-      OMLDM_KMM(24);
-      OMLDM_KMM(32);
-      OMLDM_KMM(48);
-      OMLDM_KMM(64);
-      OMLDM_KMM(96);
-      OMLDM_KMM(128);
+    OMLDM_KMM(16);
+    OMLDM_KMM(24);
+    OMLDM_KMM(32);
+    OMLDM_KMM(48);
+    OMLDM_KMM(64);
+    OMLDM_KMM(96);
+    OMLDM_KMM(128);
 #undef OMLDM_KMM
-      if (rc || !bpart) return rc;
-      return kmeans_colsum(bpart, nb, k, d, sums, counts, inertia, st);
-    }
+    if (rc || !bpart) return rc;
+    return kmeans_colsum(bpart, nb, k, d, sums, counts, inertia, st);
   }
-  const int dm = d <= 16 ? 16 : d <= 32 ? 32 : d <= 64 ? 64 : 0;
-  const size_t lds = (size_t)(k * (dm ? dm : d) + k * d + k) * 4;
-  if (lds > 150 * 1024) return -1;
   int blocks = (B + 255) / 256;
   if (blocks > kKmeansMaxBlocks) blocks = kKmeansMaxBlocks;
-  hipStream_t st = (hipStream_t)stream;
 #define OMLDM_KM(DM)                                                                        \
   do {                                                                                      \
     const int e_ = check_dyn_lds((const void*)kmeans_assign_kernel<DM>, lds);               \

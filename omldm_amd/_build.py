@@ -60,7 +60,10 @@ FILE_FLAGS = {"kmeans_seq.hip": ["-fno-slp-vectorize"],
               # a per-row chain of scalar-valued fp32 steps: nothing to pack
               "linear_poly.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               # the same chain (without the flag the compiler pairs w0 + d and the update fmas)
-              "linear_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "linear_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # MFMA tiles and LDS atomics: the default flags (195 VGPRs, no spills, at two waves
+              # per SIMD)
+              "kmeans_wide.hip": []}
 
 
 def hip_sources() -> list[str]:

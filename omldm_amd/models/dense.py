@@ -166,7 +166,13 @@ class KMeans(Learner):
     on four waves exchanging their minima through LDS; past the LDS the centroids stay in
     HBM). ``mode: "minibatch"``: assignments of a whole micro-batch against the batch-start
     centroids on the matrix cores, then c ← (n·c + Σx)/(n + m) (the same update summed over
-    the batch; tests pin its quality gap against the sequential form)."""
+    the batch; tests pin its quality gap against the sequential form).
+
+    ``predict``, the minibatch ``fit`` and, on the GPU, ``evaluate`` run on ``kmeans_assign``:
+    the LDS-resident kernels of csrc/kernels/dense_learners.hip while k centroids and their k × d
+    sums fit one workgroup's LDS (k·d up to roughly 19 000), and past that the tiled kernels of
+    csrc/kernels/kmeans_wide.hip up to k = 4096 and d = 8192 (``evaluate`` takes their inertia
+    there; at shapes the LDS-resident kernels hold it keeps ``torch.cdist``)."""
 
     NAME = "K-means"
     TASK = "clustering"
@@ -241,6 +247,12 @@ class KMeans(Learner):
 
     def evaluate(self, batch):
         x = batch.num.float()
+        if (x.is_cuda and batch.B and not D.kmeans_assign_fits(self.d, self.k)
+                and D.kmeans_wide_fits(self.d, self.k)):
+            # no B × k distance matrix in HBM: the running arg-min of the wide kernels
+            inert = torch.zeros(1, dtype=torch.float32, device=x.device)
+            D.kmeans_assign_wide(x, None, self.C, None, None, inert)
+            return inert[0], inert[0], batch.B
         dist = torch.cdist(x, self.C) ** 2
         inert = dist.min(1).values.sum()
         return inert, inert, batch.B

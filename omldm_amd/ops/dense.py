@@ -189,6 +189,9 @@ def kmeans_assign(x: torch.Tensor, y: torch.Tensor | None, cent: torch.Tensor,
     if x.is_cuda:
         from omldm_amd.ops.linear import _workspace
 
+        if not kmeans_assign_fits(d, k) and kmeans_wide_fits(d, k):
+            _kmeans_assign_wide(x, y, cent, sums, counts, inertia, assign)
+            return assign
         # per-block partials, summed per column by a second launch (csrc: kmeans_flush)
         part = _workspace(x.device, KMEANS_MAX_BLOCKS * (k * d + k + 1), key="km_part") \
             if sums is not None else None
@@ -206,6 +209,61 @@ def kmeans_assign(x: torch.Tensor, y: torch.Tensor | None, cent: torch.Tensor,
         counts.index_add_(0, a[train], torch.ones(int(train.sum())))
         if inertia is not None:
             inertia += dist[train, a[train]].sum()
+    return assign
+
+
+# ------------------------------------------------ K-means past one CU's LDS (k ≤ 4096, d ≤ 8192)
+# Tiled MFMA distances with a running arg-min, cluster sums per column slab, fixed-order folds
+# (csrc/kernels/kmeans_wide.hip). ``kmeans_assign`` sends a GPU call here exactly when the
+# LDS-resident kernels do not hold the shape; every shape they hold keeps its kernel.
+KMEANS_WIDE_MAX_K = 4096  # csrc/kernels/kmeans_wide.hip kKwMaxK
+KMEANS_WIDE_MAX_D = 8192  # csrc/kernels/kmeans_wide.hip kKwMaxD
+# calls through the wide kernels in this process (tests)
+KMEANS_WIDE_CALLS = 0
+
+
+def kmeans_assign_fits(d: int, k: int) -> bool:
+    """Whether one of the LDS-resident kernels of ``omldm_kmeans_assign`` takes k centroids of
+    d features (csrc/kernels/dense_learners.hip kmeans_assign_fit)."""
+    return bool(native.hip().omldm_kmeans_assign_fits(int(d), int(k)))
+
+
+def kmeans_wide_fits(d: int, k: int) -> bool:
+    """Whether the wide kernels take the shape: 1 ≤ k ≤ 4096, 1 ≤ d ≤ 8192."""
+    return bool(native.hip().omldm_kmeans_wide_fits(int(d), int(k)))
+
+
+def _kmeans_assign_wide(x, y, cent, sums, counts, inertia, assign) -> None:
+    from omldm_amd.ops.linear import _workspace
+
+    B, d = x.shape
+    k = cent.shape[0]
+    assert cent.is_cuda and cent.dtype == torch.float32 and cent.is_contiguous()
+    assert cent.shape[1] == d and (sums is None) == (counts is None)
+    assert y is None or (y.dtype == torch.float32 and y.is_contiguous() and y.numel() == B)
+    h = native.hip()
+    need = int(h.omldm_kmeans_wide_ws_bytes(B, d, k))
+    if need < 0:
+        raise ValueError(f"kmeans_assign_wide: k = {k}, d = {d} outside 1 ≤ k ≤ "
+                         f"{KMEANS_WIDE_MAX_K}, 1 ≤ d ≤ {KMEANS_WIDE_MAX_D}")
+    work = _workspace(x.device, (need + 3) // 4, key="km_wide")
+    global KMEANS_WIDE_CALLS
+    KMEANS_WIDE_CALLS += 1
+    check(h.omldm_kmeans_assign_wide(ptr(x), ptr(y), B, d, k, ptr(cent), ptr(sums), ptr(counts),
+                                     ptr(assign), ptr(inertia), ptr(work), work.numel() * 4,
+                                     native.stream_of(x)), "omldm_kmeans_assign_wide")
+
+
+def kmeans_assign_wide(x: torch.Tensor, y: torch.Tensor | None, cent: torch.Tensor,
+                       sums: torch.Tensor | None, counts: torch.Tensor | None,
+                       inertia: torch.Tensor | None = None, want_assign: bool = False):
+    """``kmeans_assign`` on the wide kernels, at any shape in their box (GPU tensors only):
+    the same arguments and return. ``inertia`` is added to with or without ``sums``."""
+    assert x.is_cuda and x.dim() == 2
+    B = x.shape[0]
+    assign = torch.empty(B, dtype=torch.int32, device=x.device) if want_assign else None
+    if B:
+        _kmeans_assign_wide(x.float().contiguous(), y, cent, sums, counts, inertia, assign)
     return assign
 
 

@@ -119,6 +119,10 @@ HIP_SIGS = [
     ("omldm_orr_solve_blocked_ws_bytes", i64, [i32]),
     ("omldm_orr_solve_blocked", i32, [vp, i32, i32, f64, vp, vp, i64, vp]),
     ("omldm_kmeans_assign", i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    ("omldm_kmeans_assign_fits", i32, [i32, i32]),
+    ("omldm_kmeans_wide_fits", i32, [i32, i32]),
+    ("omldm_kmeans_wide_ws_bytes", i64, [i32, i32, i32]),
+    ("omldm_kmeans_assign_wide", i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
     ("omldm_kmeans_apply", i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     ("omldm_multiclass_round", i32, [vp, i32, vp, i32, i32, vp, i32, i32, vp, i32, i32, i32, i32,
                                      i32, i32, i32, f32, i32, vp, vp, i32, vp, vp, vp, i32, vp]),
